@@ -1,12 +1,27 @@
 #!/usr/bin/env python3
 """Benchmark: the device-resident record-boundary index of BASELINE.json on 1..N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--legs fasta,csv,vcf] [--no-cpu-baseline]
-    python bench.py --workload csv|vcf ...        (one newline leg alone as the headline line)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]       (a plain run: the headline alone)
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--legs fasta,csv,vcf] [--no-cpu-baseline]
+    python bench.py [--full] --workload csv|vcf ...        (one newline leg alone as the headline line)
 
-ONE JSON line (rank 0).  Its headline is BASELINE configs[1], the FASTA '>' header index; the BASELINE
+ONE JSON line (rank 0).  Its headline is BASELINE configs[1], the FASTA '>' header index.
+
+A plain run does only what the headline figure needs: it builds and uploads the headline leg's bytes, warms up, times
+the K pipelined steps (``value``, ``ms_per_step``), writes the last step's outputs when ``--dump-outputs DIR`` is given
+and prints the line.  Everything else below is measured only with ``--full``: the event-timed and the ``serialized``
+passes over the same K steps (and with them the kernel-span check of ``value``, the roofline and the calibration
+kernels), the verification of every offset against the oracle, the CPU baselines, the ``strong`` point, the extra
+legs of ``--legs`` and the end-to-end sub-objects.  With ``--full`` the BASELINE
 configs[2] and configs[3] newline indexes ride along as the ``csv`` and ``vcf`` sub-objects of the same line
 (``--legs`` picks them; a failing leg reports ``{"error": ...}`` and never drops the headline).
+
+``--dump-outputs DIR`` (with or without ``--full``): after the timed steps, what the last pipelined step left for its
+caller -- FASTA: the (start, end) pairs, the per-chunk pending markers, chunk ends and the count; newline legs: the
+stored index's arrays, the per-range ends and the counts -- as ``DIR/<name>.npy`` (``<name>_w<k>.npy`` for worker
+k > 0) in float64 (every value is an integer below 2^53, exact).  The inputs are seeded, so two builds run with the same
+arguments write comparable files; arrays beyond the budget (DUMP_BUDGET in all) are written as a fixed seeded sample
+of their entries.
 
 Workloads (synthetic bytes of the named shapes, resident in HBM before any timed region):
   * FASTA (configs[1]): every GPU indexes its own 4 GiB FASTA object with the reference's chunk plan
@@ -39,13 +54,13 @@ Launch modes (the same worker code in both):
   * ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``: one rank per GPU; barriers and
     the final gather go over a gloo CPU group, RCCL is never initialised (nothing is exchanged).
 
-At N = 1 the line also carries two end-to-end sub-objects (tools/e2e_legs.py; never ``value``): ``e2e`` --
+At N = 1 the ``--full`` line also carries two end-to-end sub-objects (tools/e2e_legs.py; never ``value``): ``e2e`` --
 co.preprocess() of the configs[1] FASTA and of a configs[2]-shaped CSV from host memory to host memory (ranged GETs,
 pinned staging, H2D, scan, D2H, index PUT) over an in-process store and over the loopback HTTP server in its own
 process, with the stage split -- and ``fastq`` -- configs[4], a FASTQ.gz's per-read index end to end; every stored
 index read back and checked.
 
-Also in the line: per leg the scan's average span from HIP events on the device's scan stream (-> roofline:
+Also in the ``--full`` line: per leg the scan's average span from HIP events on the device's scan stream (-> roofline:
 algorithmic bytes / span vs 8 TB/s; ``traffic`` from a committed rocprofv3 PMC summary of the same command),
 the same run's read-only calibration kernel (``measured_peak``, measured behind a barrier with no worker
 scanning; null when workers share a device), for the newline legs a same-run mixed read/write reference, every
@@ -78,6 +93,12 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: event-timed and serialized passes (roofline, "
+                        "kernel-span check), calibration kernels, verification against the oracle, CPU baselines, "
+                        "the strong point, the extra legs and the end-to-end sub-objects")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the outputs of the last timed step of the headline leg as DIR/<name>.npy (float64)")
     p.add_argument("--workload", choices=list(LEGS), default="fasta",
                    help="the headline leg: fasta = configs[1] (default); csv = configs[2]; vcf = configs[3]")
     p.add_argument("--legs", default=None,
@@ -118,6 +139,8 @@ def parse(argv=None):
     if bad:
         p.error(f"unknown leg(s) {bad}")
     a.legs = [a.workload] + [x for x in legs if x != a.workload]
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     return a
 
 
@@ -303,6 +326,29 @@ def calibrate(team, fn):
     v = None if team.shared else fn()
     team.barrier()
     return v
+
+
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET = 56 << 20      # bytes of float64 written per run, all workers together (the option allows 64 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirpath, arrays, worker, world):
+    """Write every (name, array) as ``<dirpath>/<name>.npy`` (``<name>_w<k>.npy`` for worker k > 0) in float64.
+    Smallest first, an array is kept whole while it fits its share of this worker's budget (DUMP_BUDGET / world);
+    a larger one is written as a sample of its entries (rows of a 2-D array) at fixed seeded positions, in order --
+    the same positions in every run with the same arguments."""
+    os.makedirs(dirpath, exist_ok=True)
+    left = DUMP_BUDGET // 8 // world
+    todo = sorted(((n, np.atleast_1d(np.asarray(a))) for n, a in arrays), key=lambda kv: kv[1].size)
+    for i, (name, a) in enumerate(todo):
+        share = left // (len(todo) - i)
+        if a.size > share:
+            width = a.size // a.shape[0]
+            rows = np.random.default_rng(DUMP_SEED).integers(0, a.shape[0], max(1, share // width))
+            a = a[np.sort(rows)]
+        left -= a.size
+        np.save(os.path.join(dirpath, name + (f"_w{worker}" if worker else "") + ".npy"), a.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -541,7 +587,7 @@ def fasta_worker(args, team, spec: FastaSpec, strong: FastaSpec | None, k: int, 
 
     def verify(sp: FastaSpec, st, res, i_last):
         n_pairs, pending, _ = res
-        if args.no_verify:
+        if args.no_verify or not args.full:
             return None
         from oracle import dpref          # the checker (test infrastructure), outside every timed region
         g = st["g"]
@@ -559,16 +605,24 @@ def fasta_worker(args, team, spec: FastaSpec, strong: FastaSpec | None, k: int, 
     team.barrier()                    # every worker's uploads are done before any scan (shared-GPU rehearsals)
     S = st["steps"]
     S.warm(args.warmup)
-    # (1) HIP events on the device's scan stream around every scan launch: the kernels' own span
-    dt_t, (kms, kn), _ = S.timed(args.steps, timing=True)
-    # (2) the K steps with each scan also waiting for the previous step's tail (the secondary `serialized`)
-    dt, _, _ = S.timed(args.steps)
-    # (3) the K timed steps of `value`: pipelined (no events); its last result is the one verified
+    if args.full:
+        # (1) HIP events on the device's scan stream around every scan launch: the kernels' own span
+        dt_t, (kms, kn), _ = S.timed(args.steps, timing=True)
+        # (2) the K steps with each scan also waiting for the previous step's tail (the secondary `serialized`)
+        dt, _, _ = S.timed(args.steps)
+    # (3) the K timed steps of `value`: pipelined (no events); its last result is the one verified and dumped
     dt_ov, _, res = S.timed(args.steps, serialize=False)
+    if args.dump_outputs and args.workload == "fasta":
+        got = np.empty((res[0], 2), np.uint64 if spec.u64 else np.uint32)
+        ctxs[0].d2h(got, st["d_outs"][(args.steps - 1) % 2].ptr)
+        dump_outputs(args.dump_outputs, [("pairs", got), ("pending", res[1]), ("chunk_ends", res[2]),
+                                         ("count", res[0])], k, len(team.devices))
+        del got
     nbytes = st["g"].hi - st["g"].lo
-    out.update(dt=dt, dt_overlap=dt_ov, kern_s=kms / 1e3 / max(1, kn), scanned=st["scanned"], pairs=res[0],
-               alg_bytes=st["scanned"] + (16 if spec.u64 else 8) * res[0],
-               stream_peak=calibrate(team, lambda: stream_peak(ctxs[0], st["d_in"].ptr, nbytes)))
+    out.update(dt_overlap=dt_ov, scanned=st["scanned"], pairs=res[0])
+    if args.full:
+        out.update(dt=dt, kern_s=kms / 1e3 / max(1, kn), alg_bytes=st["scanned"] + (16 if spec.u64 else 8) * res[0],
+                   stream_peak=calibrate(team, lambda: stream_peak(ctxs[0], st["d_in"].ptr, nbytes)))
     if ss is not None:
         ss["steps"].warm(args.warmup)
         dts, (sms, sn), sres = ss["steps"].timed(args.steps, timing=True)
@@ -592,7 +646,7 @@ def leg_fasta(args, world, rank, devs, team):
     # index) -- N x the N = 1 workload; strong: ONE such object cut over the N GPUs by the product's split
     spec = FastaSpec(per_gpu, args.chunks, 1)
     strong = None
-    if world > 1 and not args.no_strong:
+    if world > 1 and args.full and not args.no_strong:
         strong = FastaSpec(per_gpu, args.chunks, world)
     log(f"fasta: {world} GPU(s), a {per_gpu / GiB:g} GiB FASTA per GPU, {len(spec.plan)} chunks of "
         f"{spec.chunk_size} B, {'uint64' if spec.u64 else 'uint32'} index, devices {devs} (rank {rank})")
@@ -600,13 +654,60 @@ def leg_fasta(args, world, rank, devs, team):
     return team.gather(res), spec, strong
 
 
+def plain_line(args, world, allres, t_leg, scanned, dt_ov, leg_fields):
+    """The line of a plain run (no --full): the K pipelined steps as they were measured, and what describes them.
+    The kernel-span check of ``value`` needs the event-timed pass and is part of --full."""
+    from dataplug_amd.scan import device as sdev
+    K = args.steps
+    out = {"metric": leg_fields.pop("metric"),
+           "value": round(scanned * K / dt_ov / GiB, 3),
+           "unit": "GiB/s",
+           "n_gpus": world,
+           "steps": K,
+           "warmup": args.warmup,
+           "ms_per_step": round(dt_ov / K * 1e3, 4),
+           "higher_is_better": True,
+           "vs_baseline": None,
+           "dtype": "u8",
+           "data": "synthetic",
+           "timing": "pipelined",
+           "verified_bit_exact": None}
+    out.update(leg_fields)
+    out.update({"input_placement": {"probes": [r.get("placement") for r in allres],
+                                    "slow_above": sdev.PLACEMENT_SLOW, "tries": sdev.PLACEMENT_TRIES},
+                "dumped_outputs": args.dump_outputs,
+                "gen_s": round(max(r["gen_s"] for r in allres), 2),
+                "leg_s": round(t_leg, 2),
+                "rss_gib_max_worker": max(r["rss_gib"] for r in allres)})
+    if world > 1:
+        out["per_gpu"] = [{"worker": r["worker"], "device": r["device"], "bytes": r["scanned"],
+                           "ms_per_step": round(r["dt_overlap"] / K * 1e3, 4)} for r in allres]
+    return out
+
+
+def fasta_config(spec, world, team, pairs):
+    return {"workload": f"FASTA '>' header index of a {spec.size / GiB:g} GiB synthetic object per GPU "
+                        f"(BASELINE configs[1]: chunk_size={spec.chunk_size} = size/{len(spec.plan)}), "
+                        f"{world} object(s)",
+            "object_bytes": spec.size, "objects": world, "chunks": len(spec.plan), "pairs": int(pairs),
+            "index_dtype": "uint64" if spec.u64 else "uint32",
+            "parallelism": f"independent objects x{world}, "
+                           f"{'one rank per GPU (gloo for barriers)' if team.pg is not None else 'one host thread per GPU'}, "
+                           f"no collective; one object over N GPUs: the `strong` point"}
+
+
 def report_fasta(args, world, team, allres, spec, strong, t_leg):
     from dataplug_amd.scan import device as sdev
     K = args.steps
-    dt_ser = max(r["dt"] for r in allres)
     dt_ov = max(r["dt_overlap"] for r in allres)
     scanned = sum(r["scanned"] for r in allres)
     pairs = sum(r["pairs"] for r in allres)
+    if not args.full:
+        return plain_line(args, world, allres, t_leg, scanned, dt_ov, {
+            "metric": "GiB/s scanned (device-resident) + offsets/s, FASTA index at 1/2/4/8 MI355X",
+            "scaling": "weak", "config": fasta_config(spec, world, team, pairs),
+            "offsets_per_s": round(2.0 * pairs * K / dt_ov, 1)})
+    dt_ser = max(r["dt"] for r in allres)
     kern = max(r["kern_s"] for r in allres)
     # one scan at a time per GPU: a step is never shorter than its scan.  A pipelined run measured below the scan's
     # own event-timed span (which carries the events' cost) counts every step at that span ("kernel-bound")
@@ -651,14 +752,7 @@ def report_fasta(args, world, team, allres, spec, strong, t_leg):
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic",
-        "config": {"workload": f"FASTA '>' header index of a {spec.size / GiB:g} GiB synthetic object per GPU "
-                               f"(BASELINE configs[1]: chunk_size={spec.chunk_size} = size/{len(spec.plan)}), "
-                               f"{world} object(s)",
-                   "object_bytes": spec.size, "objects": world, "chunks": len(spec.plan), "pairs": int(pairs),
-                   "index_dtype": "uint64" if spec.u64 else "uint32",
-                   "parallelism": f"independent objects x{world}, "
-                                  f"{'one rank per GPU (gloo for barriers)' if team.pg is not None else 'one host thread per GPU'}, "
-                                  f"no collective; one object over N GPUs: the `strong` point"},
+        "config": fasta_config(spec, world, team, pairs),
         "offsets_per_s": round(2.0 * pairs * K / dt, 1),
         "timing": "pipelined" if pipelined else "kernel-bound",
         "serialized": {"value": round(scanned * K / dt_ser / GiB, 3), "unit": "GiB/s",
@@ -801,12 +895,31 @@ def delim_worker(args, team, leg, k, world, dev):
     S = Steps(team, ctxs, launch, collect)
     team.barrier()
     S.warm(args.warmup)
-    dt_t, (kms, kn), _ = S.timed(args.steps, timing=True)
+    if args.full:
+        dt_t, (kms, kn), _ = S.timed(args.steps, timing=True)
+        dt, _, _ = S.timed(args.steps)                                     # serialized (secondary)
+    dt_ov, _, (n_out, n_seen, ends) = S.timed(args.steps, serialize=False)  # pipelined (`value`), verified, dumped
     # the kernel the timed launches ran: line_kernel up to 4 GiB per launch, above it the density probe's pick from
     # the launch's own bytes (dp_last_delim_form reads it back with each launch's results)
     kernel = " / ".join(ScanContext.DELIM_FORMS[f] for f in sorted({c.last_delim_form() for c in ctxs}))
-    dt, _, _ = S.timed(args.steps)                                         # serialized (secondary)
-    dt_ov, _, (n_out, _, ends) = S.timed(args.steps, serialize=False)      # pipelined (`value`), verified
+    np_item = {"u8s": np.uint8, "u16b": np.uint16, "u32p": np.uint32, "u64": np.uint64}[fmt]
+    if args.dump_outputs and leg == args.workload:
+        last = d_outs[(args.steps - 1) % 2].ptr
+        arrays = [("offsets_low" if fmt != "u64" else "offsets", ctxs[0].d2h(np.empty(n_out, np_item), last)),
+                  ("range_ends", ends), ("count", n_out), ("delims_seen", n_seen)]
+        if fmt in ("u8s", "u16b"):
+            arrays.append(("block_table", ctxs[0].block_table(last, cap, rg, mode)))
+        if fmt == "u8s":
+            arrays.append(("sub_table", ctxs[0].sub_table(last, cap, rg)))
+        dump_outputs(args.dump_outputs, arrays, k, world)
+        del arrays
+    if not args.full:
+        out = {"worker": k, "device": dev, "dt_overlap": dt_ov, "scanned": nbytes, "offsets": n_out, "kernel": kernel,
+               "gen_s": gen_s, "size": size, "placement": list(ctxs[0].placements)}
+        for c in ctxs:
+            c.close()
+        out["rss_gib"] = peak_rss_gib()
+        return out
     wpr = item * n_out / max(1, nbytes)
     d_mix = ctxs[0].workspace("bench_mix", int(wpr * nbytes) + (1 << 20))
     peak = calibrate(team, lambda: stream_peak(ctxs[0], d_buf.ptr, nbytes))
@@ -814,8 +927,7 @@ def delim_worker(args, team, leg, k, world, dev):
     verified, t_ver = None, time.perf_counter()
     if not args.no_verify:
         last = d_outs[(args.steps - 1) % 2].ptr
-        got = ctxs[0].d2h(np.empty(n_out, {"u8s": np.uint8, "u16b": np.uint16, "u32p": np.uint32, "u64": np.uint64}[fmt]),
-                          last)
+        got = ctxs[0].d2h(np.empty(n_out, np_item), last)
         with _VERIFY_SLOTS:
             if fmt == "u8s":
                 verified = n_out == n_exp and _verify_bytes(obj, begin, end, got, ctxs[0].sub_table(last, cap, rg),
@@ -862,10 +974,26 @@ def report_delim(args, world, team, allres, leg, t_leg, headline: bool):
     csv_mode = leg == "csv"
     K = args.steps
     size = allres[0]["size"]
-    dt_ser = max(r["dt"] for r in allres)
     dt_ov = max(r["dt_overlap"] for r in allres)
     scanned = sum(r["scanned"] for r in allres)
     offs = sum(r["offsets"] for r in allres)
+    name = "CSV" if csv_mode else "VCF"
+    idx = {"u8s": "uint8 low bytes + 256-byte counts + 64 KiB block table",
+           "u16b": "uint16 low words + 64 KiB block table", "u32p": "uint32 low words + 4 GiB pages",
+           "u64": "uint64"}[args.index_dtype]
+    cfg = (f"'\\n' index ({idx}), {size / GiB:g} GiB cities.csv-shaped object per GPU (BASELINE configs[2])"
+           if csv_mode else
+           f"'\\n' index ({idx}) of one {size / GiB:g} GiB VCF body cut into {world} part(s), one per GPU "
+           f"(BASELINE configs[3])")
+    config = {"workload": cfg, "object_bytes": size, "scanned_bytes_per_gpu": allres[0]["scanned"],
+              "offsets_per_gpu": int(allres[0]["offsets"]),
+              "parallelism": f"independent {'objects' if csv_mode else 'body parts'} x{world}, no collective"}
+    if not args.full:
+        return plain_line(args, world, allres, t_leg, scanned, dt_ov, {
+            "metric": f"GiB/s scanned (device-resident) + offsets/s, {name} newline index",
+            "scaling": "weak" if csv_mode else "strong", "config": config,
+            "offsets_per_s": round(offs * K / dt_ov, 1), "kernel": allres[0]["kernel"]})
+    dt_ser = max(r["dt"] for r in allres)
     kern = max(r["kern_s"] for r in allres)
     # one scan at a time per GPU: a step is never shorter than its scan.  A pipelined run measured below the scan's
     # own event-timed span (which carries the events' cost) counts every step at that span ("kernel-bound")
@@ -888,14 +1016,6 @@ def report_delim(args, world, team, allres, leg, t_leg, headline: bool):
     pmc_kernel = "line_kernel<" if k.startswith("line_kernel") else "scan_kernel<1"
     traffic, traffic_src = (load_traffic(args, leg, allres[0]["scanned"], pmc_kernel, args.index_dtype)
                             if world == 1 else (None, None))
-    name = "CSV" if csv_mode else "VCF"
-    idx = {"u8s": "uint8 low bytes + 256-byte counts + 64 KiB block table",
-           "u16b": "uint16 low words + 64 KiB block table", "u32p": "uint32 low words + 4 GiB pages",
-           "u64": "uint64"}[args.index_dtype]
-    cfg = (f"'\\n' index ({idx}), {size / GiB:g} GiB cities.csv-shaped object per GPU (BASELINE configs[2])"
-           if csv_mode else
-           f"'\\n' index ({idx}) of one {size / GiB:g} GiB VCF body cut into {world} part(s), one per GPU "
-           f"(BASELINE configs[3])")
     verified = None if args.no_verify else all(r["verified"] for r in allres)
     out = {
         "metric": f"GiB/s scanned (device-resident) + offsets/s, {name} newline index",
@@ -904,9 +1024,7 @@ def report_delim(args, world, team, allres, leg, t_leg, headline: bool):
         "n_gpus": world,
         "ms_per_step": round(dt / K * 1e3, 4),
         "scaling": "weak" if csv_mode else "strong",
-        "config": {"workload": cfg, "object_bytes": size, "scanned_bytes_per_gpu": allres[0]["scanned"],
-                   "offsets_per_gpu": int(allres[0]["offsets"]),
-                   "parallelism": f"independent {'objects' if csv_mode else 'body parts'} x{world}, no collective"},
+        "config": config,
         "offsets_per_s": round(offs * K / dt, 1),
         "timing": "pipelined" if pipelined else "kernel-bound",
         "serialized": {"value": round(scanned * K / dt_ser / GiB, 3), "unit": "GiB/s",
@@ -968,7 +1086,7 @@ def main(argv=None):
     t_all = time.perf_counter()
     try:
         head = run_leg(args, world, rank, devs, team, args.workload, True)   # the headline: errors propagate
-        for leg in args.legs[1:]:
+        for leg in args.legs[1:] if args.full else ():      # a plain run is the headline leg alone
             try:
                 sub = run_leg(args, world, rank, devs, team, leg, False)
             except Exception as e:            # a failing extra leg never drops the headline line
@@ -979,7 +1097,7 @@ def main(argv=None):
                 team._tb.reset()              # a failed worker aborted the threads' barrier
             if head is not None:
                 head[leg] = sub
-        if world == 1 and not args.no_e2e and head is not None:
+        if args.full and world == 1 and not args.no_e2e and head is not None:
             sys.path.insert(0, os.path.join(REPO, "tools"))
             import e2e_legs
             budgets = {"e2e": 90.0, "fastq": 45.0}
@@ -1000,6 +1118,7 @@ def main(argv=None):
         if head is not None:
             rss = [head.get("rss_gib_max_worker", 0.0)] + [(head.get(x) or {}).get("rss_gib_max_worker", 0.0)
                                                            for x in args.legs[1:]]
+            head["full"] = args.full
             head["peak_rss_gib"] = max([peak_rss_gib()] + [r or 0.0 for r in rss])
             head["bench_wall_s"] = round(time.perf_counter() - t_all, 2)
             print(json.dumps(head), flush=True)

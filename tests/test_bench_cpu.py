@@ -21,6 +21,36 @@ def test_legs():
         bench.parse(["--legs", "fasta,gff"])
 
 
+def test_plain_run_by_default_full_on_request():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_float64_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    pairs = np.arange(40000, dtype=np.uint32).reshape(-1, 2) * np.uint32(100000)      # values up to 4e9: exact in f64
+    arrays = [("pairs", pairs), ("pending", np.full(4, -1, np.int64)), ("count", len(pairs))]
+    bench.dump_outputs(str(tmp_path / "a"), arrays, 0, 1)
+    got = np.load(tmp_path / "a" / "pairs.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, pairs.astype(np.float64))
+    assert np.load(tmp_path / "a" / "count.npy").tolist() == [20000.0]
+    assert np.load(tmp_path / "a" / "pending.npy").tolist() == [-1.0] * 4
+    # beyond the budget: the small arrays whole, the large one as the same ordered sample of rows in every run
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8 * 3000)
+    for d, worker in (("b", 0), ("c", 0), ("d", 1)):
+        bench.dump_outputs(str(tmp_path / d), arrays, worker, 1)
+    b, c = np.load(tmp_path / "b" / "pairs.npy"), np.load(tmp_path / "c" / "pairs.npy")
+    assert np.array_equal(b, c) and b.shape[1] == 2 and 1000 <= len(b) <= 1500
+    assert (np.diff(b[:, 0]) >= 0).all() and {tuple(x) for x in b} <= {tuple(x) for x in pairs.astype(np.float64)}
+    assert np.load(tmp_path / "b" / "pending.npy").tolist() == [-1.0] * 4
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 8 * 3000 + 3 * 128                                                 # + the .npy headers
+    assert sorted(os.listdir(tmp_path / "d")) == ["count_w1.npy", "pairs_w1.npy", "pending_w1.npy"]
+
+
 def test_pool_plan_reports_its_basis():
     n, host = bench.pool_plan()
     assert n == host["pool_processes"] >= 1

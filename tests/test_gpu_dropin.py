@@ -356,7 +356,7 @@ def test_bench_thread_mode_split_on_one_gpu(tmp_path):
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "4", "--devices", "0,0,0,0",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "4", "--devices", "0,0,0,0",
            "--size", str((48 << 20) + 4096), "--csv-size", str((40 << 20) + 77), "--vcf-size", str((96 << 20) + 5),
            "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=repo)
@@ -386,7 +386,7 @@ def test_bench_default_line_carries_the_newline_legs():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--size", str((64 << 20) + 12), "--csv-size",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--size", str((64 << 20) + 12), "--csv-size",
            str((72 << 20) + 3), "--vcf-size", str((80 << 20) + 9), "--steps", "3", "--warmup", "1",
            "--e2e-fasta-size", str((48 << 20) + 5), "--e2e-csv-size", str((40 << 20) + 7), "--fastq-tiles", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=repo)
@@ -419,6 +419,37 @@ def test_bench_default_line_carries_the_newline_legs():
     assert line["bench_wall_s"] > 0
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the K pipelined steps of the headline leg and nothing else in the line; with
+    --dump-outputs the last step's index lands as float64 .npy files and equals the oracle's pairs."""
+    import subprocess
+    import sys
+    from oracle import cpu_ref, dpref
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    size = (24 << 20) + 12
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--size", str(size), "--steps", "3",
+           "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120, cwd=repo)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    # value is the object's bytes per timed step; ms_per_step is rounded to 1e-4 ms of a step of 0.01 ms or more
+    assert line["value"] == pytest.approx(size / (line["ms_per_step"] / 1e3) / (1 << 30), rel=0.01)
+    for moved in ("csv", "vcf", "e2e", "fastq", "cpu_baseline", "roofline", "serialized", "strong"):
+        assert moved not in line, moved
+    plan = cpu_ref.chunk_plan(size, size // 4)                # bench.py's plan: chunk_size = size / 4, seed 1
+    exp = dpref.fasta_pairs(synth.TiledFasta(size, seed=1).bytes_range(0, size), plan)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == ["chunk_ends", "count", "pairs", "pending"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["pairs"], exp.astype(np.float64)) and got["count"].tolist() == [len(exp)]
+    assert (got["pending"] == -1).all() and len(got["chunk_ends"]) == len(plan) == 4
+
+
 @pytest.mark.parametrize("workload", ["fasta", "vcf"])
 def test_bench_under_torch_distributed_run(workload):
     """The driver's N > 1 launch (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N),
@@ -433,8 +464,8 @@ def test_bench_under_torch_distributed_run(workload):
         s_.bind(("127.0.0.1", 0))
         port = s_.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--devices", "0,0",
-           "--workload", workload, "--fasta-size", str(256 << 20), "--legs", "fasta,vcf",
+           "127.0.0.1", "--master-port", str(port), os.path.join(repo, "bench.py"), "--full", "--gpus", "2",
+           "--devices", "0,0", "--workload", workload, "--fasta-size", str(256 << 20), "--legs", "fasta,vcf",
            "--vcf-size", str((200 << 20) + 1),
            "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")

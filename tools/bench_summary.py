@@ -14,10 +14,10 @@ for path in sys.argv[1:]:
         if "error" in x:
             print(f"{path} {name}: ERROR {x['error']}")
             continue
-        r = x["roofline"]
+        r = x.get("roofline") or {}                      # a plain run (no --full) has the headline figure alone
         cpu = x.get("cpu_baseline") or {}
-        print(f"{path} {name}: value {x['value']} {x['unit']}, {x['ms_per_step']} ms/step, span {r['kernel_avg_us']} us, "
-              f"frac {r['frac']}, of read ceiling {r.get('frac_of_measured_peak')}, of mixed ref "
+        print(f"{path} {name}: value {x['value']} {x['unit']}, {x['ms_per_step']} ms/step, span {r.get('kernel_avg_us')} us, "
+              f"frac {r.get('frac')}, of read ceiling {r.get('frac_of_measured_peak')}, of mixed ref "
               f"{r.get('frac_of_mixed_ref')}, traffic {r.get('traffic')} ({r.get('traffic_source')}), verified "
               f"{x.get('verified_bit_exact', x.get('verified_every_offset'))}, cpu {cpu.get('value')} on "
               f"{cpu.get('cores')} cores, leg {x.get('leg_s')} s")

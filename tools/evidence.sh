@@ -24,7 +24,7 @@ for leg in $LEGS; do
 done
 if [ -z "$NO_BENCH" ]; then
   step bench
-  timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
   python3 tools/bench_summary.py $O/bench.json
 fi
 step done

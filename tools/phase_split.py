@@ -2,7 +2,7 @@
 
     python tools/phase_split.py gpurun_out/prof_<tag> profiles/<tag> --warmup W --steps K [--mode 0|1]
 
-bench.py launches the scan max(2, W) times untimed, then K times with HIP events around each launch (the
+bench.py --full launches the scan max(2, W) times untimed, then K times with HIP events around each launch (the
 roofline phase), K times serialized (the secondary `serialized` field) and K times pipelined (the `value`
 phase).  rocprofv3's --stats average mixes all of them; the roofline-phase average is the one that must
 agree with bench.py's `roofline.kernel_avg_us`.

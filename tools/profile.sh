@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {  # name, rocprof args...
   local name=$1; shift
   timeout -k 10 240 rocprofv3 "$@" -d "$OUT/$name" -o "$name" --output-format csv -- \
-      python3 "$ROOT/bench.py" $ARGS > "$OUT/$name.log" 2>&1
+      python3 "$ROOT/bench.py" --full $ARGS > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "$name rc=$rc" >> "$OUT/status.txt"
   return $rc
