@@ -1,4 +1,4 @@
-"""Build libdpscan.so in-tree for gfx950:  python -m dataplug_amd.build
+"""Build libdpscan.so and libdpquote.so in-tree for gfx950:  python -m dataplug_amd.build
 
 The scan library is compiled with -save-temps and the ISA guard (dataplug_amd/isa_guard.py) checks that exact
 device assembly: every kernel, no touched in-flight load destination, no scratch segment.  Only a library that
@@ -22,6 +22,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "dpscan.hip")
 OUT = os.path.join(HERE, "lib", "libdpscan.so")
 OUT_DIAG = os.path.join(HERE, "lib", "libdpscan_diag.so")   # diagnostics: in-kernel realtime stamps (-DDP_DIAG)
+QUOTE_SRC = os.path.join(HERE, "csrc", "dpquote.hip")      # quote-aware CSV record index (include/dpquote.h)
+QUOTE_OUT = os.path.join(HERE, "lib", "libdpquote.so")
+QUOTE_REQUIRED = ("quote_kernel",)                         # the kernels libdpquote.so must contain
 GZ_SRC = os.path.join(HERE, "csrc", "dpgz.c")
 GZ_PAR_SRC = os.path.join(HERE, "csrc", "dpgz_par.c")     # parallel inflate of one gzip stream
 GZ_OUT = os.path.join(HERE, "lib", "libdpgz.so")            # host-side gzip access-point index (zlib)
@@ -44,10 +47,12 @@ def stamp_path(lib: str) -> str:
     return lib + ".isa.json"
 
 
-def build(verbose: bool = False, diag: bool = False, defines=(), out=None, src=SRC) -> str:
+def build(verbose: bool = False, diag: bool = False, defines=(), out=None, src=SRC,
+          required=isa_guard.REQUIRED) -> str:
     """Compile ``src`` for gfx950, run the ISA guard on its assembly, install it at ``out`` only if it passes.
     The shipped library has no defines; ``diag`` builds the diagnostics library (-DDP_DIAG: in-kernel realtime
-    stamps, lib/libdpscan_diag.so), guarded like the shipped one and loaded only through DPSCAN_LIB."""
+    stamps, lib/libdpscan_diag.so), guarded like the shipped one and loaded only through DPSCAN_LIB.  ``required``:
+    the kernels the guard insists on finding in the code object."""
     out = out or (OUT_DIAG if diag else OUT)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
@@ -61,7 +66,7 @@ def build(verbose: bool = False, diag: bool = False, defines=(), out=None, src=S
         subprocess.run(cmd, check=True, cwd=d)
         stem = os.path.splitext(os.path.basename(src))[0]
         asm = os.path.join(d, f"{stem}-hip-amdgcn-amd-amdhsa-{ARCH}.s")
-        rep = isa_guard.verify(asm)
+        rep = isa_guard.verify(asm, required=required)
         print(f"ISA guard: {rep['result']} ({len(rep['kernels'])} kernels, {os.path.basename(out)})",
               file=sys.stderr if rep["result"] != "ok" else sys.stdout, flush=True)
         if rep["result"] != "ok":
@@ -78,6 +83,12 @@ def build(verbose: bool = False, diag: bool = False, defines=(), out=None, src=S
     return out
 
 
+def build_quote(verbose: bool = False) -> str:
+    """libdpquote.so: the same hipcc line with -save-temps, the ISA guard on that exact assembly (its own kernel
+    list), installed with its ``.isa.json`` stamp only on "ok"."""
+    return build(verbose=verbose, out=QUOTE_OUT, src=QUOTE_SRC, required=QUOTE_REQUIRED)
+
+
 def build_gz() -> str:
     os.makedirs(os.path.dirname(GZ_OUT), exist_ok=True)
     cc = os.environ.get("CC", "gcc")
@@ -90,3 +101,4 @@ def build_gz() -> str:
 if __name__ == "__main__":
     print(build_gz())
     print(build(verbose="-v" in sys.argv, diag="--diag" in sys.argv))
+    print(build_quote(verbose="-v" in sys.argv))

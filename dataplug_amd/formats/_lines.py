@@ -23,6 +23,7 @@ from ..storage.errors import ClientError
 from ..version import __version__
 
 LINES_SUFFIX = ".lines"
+RECORDS_SUFFIX = ".records"        # quote-aware record ends (uint64 LE), beside the newline index
 _PRELOAD_BYTES = 256 << 20
 _BLOCK = 8192                      # entries per cached block for large indexes
 
@@ -220,6 +221,38 @@ def index_object(cloud_object, begin: int = 0, index_format: str = "auto", piece
         finally:
             pieces.close()
     return store_line_index(cloud_object, so.line_index_object(cloud_object, begin=begin, end=end, fmt=fmt))
+
+
+def store_record_index(cloud_object, offsets, quotechar: str) -> dict:
+    """PUT the quote-aware record ends (``scan.objects.record_index_object``) as uint64 LE at ``<key>.records``,
+    beside the newline index; returns the attributes that describe it."""
+    key = cloud_object.meta_path.key + RECORDS_SUFFIX
+    cloud_object.storage.put_object(Body=np.ascontiguousarray(offsets, "<u8").tobytes(),
+                                    Bucket=cloud_object.meta_path.bucket, Key=key,
+                                    Metadata={"dataplug": __version__})
+    return {"record_index_key": key, "num_records": int(len(offsets)), "quotechar": quotechar}
+
+
+def records_of(cloud_object) -> "LineIndex":
+    """The stored record ends of an object preprocessed with ``quotechar`` (``nxt(x)`` = 1 + the first record end
+    at or after x)."""
+    attrs = cloud_object.attributes
+    key = getattr(attrs, "record_index_key", None) if attrs is not None else None
+    if not key:
+        raise KeyError(f"{cloud_object!r} has no record index: preprocess it with "
+                       f"extra_args={{'quotechar': '\"'}}")
+    return LineIndex(storage=cloud_object.storage, bucket=cloud_object.meta_path.bucket, key=key,
+                     count=getattr(attrs, "num_records", None))
+
+
+def snap(records: "LineIndex", size: int, x: int) -> int:
+    """The smallest boundary >= x of B = {0} | {e + 1 for record ends e} | {size}."""
+    if x <= 0:
+        return 0
+    if x >= size:
+        return size
+    n = records.nxt(x - 1)             # e + 1 >= x  <=>  e >= x - 1
+    return size if n is None else min(n, size)
 
 
 class LineIndex:

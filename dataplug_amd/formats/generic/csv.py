@@ -7,6 +7,11 @@ csv.py:20-36) and additionally stores the sorted offsets of every ``'\\n'`` (sca
 object itself stays empty, as in the reference.  The partition strategies produce the reference's
 ``range_0``/``range_1`` and a ``get()`` with identical output, resolved from the index instead of a
 padded Python scan per slice (the reference's formulas: ``_lines.csv_body``).
+
+Opt-in, beyond the reference: ``preprocess(extra_args={"quotechar": '"'})`` also stores the quote-aware record ends
+(the ``'\\n'`` outside quoted fields, RFC 4180; built on the GPU by libdpquote.so) as uint64 at ``<key>.records``
+(attributes ``record_index_key``, ``num_records``, ``quotechar``), and ``partition_records_num_chunks`` /
+``partition_records_chunk_size`` cut only at record ends, so a line break inside a quoted field never splits a row.
 """
 from __future__ import annotations
 
@@ -17,7 +22,7 @@ from typing import TYPE_CHECKING, List, Optional
 
 from ...entities import CloudDataFormat, CloudObjectSlice, PartitioningStrategy
 from ...preprocessing.metadata import PreprocessingMetadata
-from .._lines import LineIndex, SliceError, csv_body, index_object, slice_error
+from .._lines import LineIndex, SliceError, csv_body, index_object, records_of, slice_error, snap, store_record_index
 
 if TYPE_CHECKING:
     from ...cloudobject import CloudObject
@@ -26,17 +31,30 @@ logger = logging.getLogger(__name__)
 
 
 def preprocess_csv(cloud_object: "CloudObject", separator: str = ",", line_index: bool = True,
-                   index_format: str = "auto") -> PreprocessingMetadata:
+                   index_format: str = "auto", quotechar: Optional[str] = None) -> PreprocessingMetadata:
     import pandas as pd
 
     top = []
     with cloud_object.open("r") as f:
         for _ in range(20):
             top.append(f.readline().strip())
-    df = pd.read_csv(io.StringIO("\n".join(top)), sep=separator)
+        if quotechar is not None:
+            # the sample must end at a record end: read on while it stops inside a quoted field
+            while sum(t.count(quotechar) for t in top) % 2 and len(top) < 4096:
+                line = f.readline()
+                if not line:
+                    break
+                top.append(line.strip())
+    df = pd.read_csv(io.StringIO("\n".join(top)), sep=separator, **({} if quotechar is None else {"quotechar": quotechar}))
     attrs = {"columns": df.columns.tolist(), "dtypes": df.dtypes.tolist()}
     if line_index:
         attrs.update(index_object(cloud_object, 0, index_format))
+    if quotechar is not None:
+        q = quotechar.encode("utf-8")
+        if len(q) != 1 or q == b"\n":
+            raise ValueError(f"quotechar must be one byte other than a newline, not {quotechar!r}")
+        from ...scan import objects as so
+        attrs.update(store_record_index(cloud_object, so.record_index_object(cloud_object, quote=q[0]), quotechar))
     return PreprocessingMetadata(attributes=attrs)
 
 
@@ -108,3 +126,27 @@ def partition_chunk_size(cloud_object: "CloudObject", chunk_size: int, padding: 
 def partition_num_chunks(cloud_object: "CloudObject", num_chunks: int, padding: int = 256) -> List[CSVSlice]:
     """csv.py:132-148."""
     return _slices(cloud_object, ceil(cloud_object.size / num_chunks), num_chunks, padding)
+
+
+def _record_slices(cloud_object, chunk_size: int, num_chunks: int) -> List[CSVSlice]:
+    """Slice i = [snap(i * chunk_size), snap((i + 1) * chunk_size)) over the record boundaries (``_lines.snap``):
+    the bodies tile the object, each ends at a record end (or the object's end), and may be empty."""
+    size = cloud_object.size
+    records = records_of(cloud_object)
+    cuts = [snap(records, size, min(size, i * chunk_size)) for i in range(num_chunks)] + [size]
+    return [CSVSlice(range_0=cuts[i], range_1=cuts[i + 1], chunk_id=i, num_chunks=num_chunks, padding=0,
+                     body=(cuts[i], cuts[i + 1])) for i in range(num_chunks)]
+
+
+@PartitioningStrategy(dataformat=CSV)
+def partition_records_chunk_size(cloud_object: "CloudObject", chunk_size: int) -> List[CSVSlice]:
+    """Slices of about ``chunk_size`` bytes cut at quote-aware record ends (needs ``quotechar`` at preprocess)."""
+    assert 0 < chunk_size <= cloud_object.size, "Chunk size must be positive and at most the file size"
+    return _record_slices(cloud_object, chunk_size, ceil(cloud_object.size / chunk_size))
+
+
+@PartitioningStrategy(dataformat=CSV)
+def partition_records_num_chunks(cloud_object: "CloudObject", num_chunks: int) -> List[CSVSlice]:
+    """``num_chunks`` slices cut at quote-aware record ends (needs ``quotechar`` at preprocess)."""
+    assert num_chunks > 0, "num_chunks must be positive"
+    return _record_slices(cloud_object, max(1, ceil(cloud_object.size / num_chunks)), num_chunks)

@@ -200,13 +200,14 @@ def short_name(sym: str) -> str:
     return base + "<" + ",".join(re.findall(r"Li(\d+)E", targs.group(1))) + ">"
 
 
-def verify(asm_path: str) -> dict:
-    """The guard's verdict on one assembly file: every kernel checked, the violations and scratch segments."""
+def verify(asm_path: str, required=REQUIRED) -> dict:
+    """The guard's verdict on one assembly file: every kernel checked, the violations and scratch segments.
+    ``required``: the kernel names the code object must contain (default: libdpscan's)."""
     kernels = kernel_names(asm_path)
     bad = check(asm_path)
     spills = scratch(asm_path)
     names = [short_name(k) for k in kernels]
-    missing = [r for r in REQUIRED if not any(n.split("<")[0] == r for n in names)]
+    missing = [r for r in required if not any(n.split("<")[0] == r for n in names)]
     ok = not bad and not spills and not missing
     return {"result": "ok" if ok else "FAIL", "kernels": names,
             "violations": [f"{short_name(k)}: {s}" for k, s in bad[:20]], "n_violations": len(bad),

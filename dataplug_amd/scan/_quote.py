@@ -1,0 +1,83 @@
+"""ctypes binding of libdpquote.so (the C ABI declared in include/dpquote.h): the quote-aware CSV record index.
+
+Built in-tree by ``dataplug_amd.build.build_quote()`` into ``dataplug_amd/lib/libdpquote.so``.  The refusal rules
+are those of ``_lib.py``: there is NO fallback -- a missing or unloadable library raises ``DPScanUnavailable``, and
+so does one whose ISA-guard stamp (``<lib>.isa.json``) is missing, failed or belongs to another file.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+from ._lib import DPCapacityError, DPScanError, DPScanUnavailable, guard_check
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("DPQUOTE_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libdpquote.so"))
+
+DQ_OK = 0
+DQ_ERR_INVALID = 1
+DQ_ERR_HIP = 2
+DQ_ERR_CAPACITY = 3
+DQ_ERR_OVERFLOW = 4
+DQ_ERR_TIMEOUT = 5
+
+# (name, restype, argtypes) for every symbol include/dpquote.h declares
+_c = ctypes
+_p = _c.c_void_p
+_u64 = _c.c_uint64
+_u64p = _c.POINTER(_c.c_uint64)
+SIGNATURES = [
+    ("dq_abi_version", _c.c_int, []),
+    ("dq_last_error", _c.c_char_p, []),
+    ("dq_ctx_create", _c.c_int, [_c.c_int, _p, _c.POINTER(_p)]),
+    ("dq_ctx_destroy", _c.c_int, [_p]),
+    ("dq_records_async", _c.c_int, [_p, _p, _u64, _u64, _u64, _u64, _c.c_uint32, _c.c_uint32, _p, _c.c_int, _u64]),
+    ("dq_records_result", _c.c_int, [_p, _u64p, _u64p, _u64p]),
+    ("dq_geometry", _c.c_int, [_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+]
+
+_lib = None
+ABI_VERSION = 1                          # include/dpquote.h DQ_ABI_VERSION
+
+
+def load(path: str = None):
+    """Load libdpquote.so once (raises DPScanUnavailable); ``path`` loads another file, uncached (tests)."""
+    global _lib
+    if path is None and _lib is not None:
+        return _lib
+    p = path or LIB_PATH
+    if not os.path.exists(p):
+        raise DPScanUnavailable(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; "
+                                f"g.build()'` (hipcc --offload-arch=gfx950)")
+    guard_check(p)
+    try:
+        lib = ctypes.CDLL(p)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise DPScanUnavailable(f"cannot load {p}: {e}") from e
+    for name, res, args in SIGNATURES:
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise DPScanUnavailable(f"{p} does not export {name}: rebuild it")
+        fn.restype = res
+        fn.argtypes = args
+    ver = int(lib.dq_abi_version())
+    if ver != ABI_VERSION:
+        raise DPScanUnavailable(f"{p} has ABI version {ver}, this binding needs {ABI_VERSION}: rebuild it")
+    if path is None:
+        _lib = lib
+    return lib
+
+
+def last_error() -> str:
+    return (load().dq_last_error() or b"").decode(errors="replace")
+
+
+def check(rc: int) -> None:
+    if rc == DQ_OK:
+        return
+    msg = last_error()
+    if rc == DQ_ERR_OVERFLOW:
+        raise OverflowError(msg or "Python integer out of bounds for uint32")
+    if rc == DQ_ERR_CAPACITY:
+        raise DPCapacityError(rc, msg)
+    raise DPScanError(rc, msg)

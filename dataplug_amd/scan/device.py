@@ -97,6 +97,7 @@ class ScanContext:
         self._get_pool = None
         self._timing_on = False
         self.placements = []                          # per placed buffer: the probe ratios of its candidates
+        self._dq = None                               # libdpquote's dq_ctx on this context's stream (record_ends)
 
     # ---------------------------------------------------------------- memory
     def workspace(self, name: str, nbytes: int, placed: bool = False) -> DeviceBuffer:
@@ -399,6 +400,70 @@ class ScanContext:
                 return vals, nd, ends, self.block_table(out.ptr, cap, rg, 4), self.sub_table(out.ptr, cap, rg)
             return vals, nd, ends
 
+    # ---------------------------------------------------------------- quote-aware record ends (libdpquote.so)
+    def _quote_ctx(self):
+        """The context's ``dq_ctx``, created on first use on the context's current stream."""
+        from . import _quote
+        if self._dq is None:
+            h = ctypes.c_void_p()
+            _quote.check(_quote.load().dq_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
+            self._dq = h
+        return _quote.load(), self._dq
+
+    def quote_geometry(self) -> Tuple[int, int]:
+        """(tile bytes, workgroups of the persistent grid) of the record-end kernel (dq_geometry)."""
+        from . import _quote
+        q, h = self._quote_ctx()
+        g = ctypes.c_int(0)
+        t = ctypes.c_int(0)
+        _quote.check(q.dq_geometry(h, ctypes.byref(g), ctypes.byref(t)))
+        return int(t.value), int(g.value)
+
+    def record_ends_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int,
+                          carry: int, d_out: int, u64: bool, cap: int) -> None:
+        from . import _quote
+        q, h = self._quote_ctx()
+        _quote.check(q.dq_records_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote),
+                                        int(carry), ctypes.c_void_p(d_out or 0), int(u64), int(cap)))
+
+    def record_ends_result(self) -> Tuple[int, int, int]:
+        """(record ends, quote bytes, newlines) of the launch in flight; DPCapacityError carries ``needed``."""
+        from . import _quote
+        q, h = self._quote_ctx()
+        n, nq, nn = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = q.dq_records_result(h, ctypes.byref(n), ctypes.byref(nq), ctypes.byref(nn))
+        if rc == _quote.DQ_ERR_CAPACITY:
+            e = DPCapacityError(rc, _quote.last_error())
+            e.needed, e.n_quotes, e.n_newlines = int(n.value), int(nq.value), int(nn.value)
+            raise e
+        _quote.check(rc)
+        return int(n.value), int(nq.value), int(nn.value)
+
+    def record_counts(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
+                      carry: int = 0) -> Tuple[int, int, int]:
+        """The count-only launch: (record ends, quote bytes, newlines) of object bytes [begin, end)."""
+        self.record_ends_async(d_buf, buf_len, buf_base, begin, end, quote, carry, 0, True, 0)
+        return self.record_ends_result()
+
+    def record_ends(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
+                    carry: int = 0, u64: bool = True, cap: Optional[int] = None):
+        """Sorted object offsets of the '\\n' that end a CSV record in object bytes [begin, end): those with an even
+        number of ``quote`` bytes (plus ``carry``) before them (dq_records_async; include/dpquote.h).
+
+        Returns (offsets uint64|uint32, quote bytes seen, newlines seen)."""
+        dtype = np.uint64 if u64 else np.uint32
+        if cap is None:
+            cap = (end - begin) // 16 + 1024
+        while True:
+            out = self.workspace("out", cap * np.dtype(dtype).itemsize + 16)
+            self.record_ends_async(d_buf, buf_len, buf_base, begin, end, quote, carry, out.ptr, u64, cap)
+            try:
+                n, nq, nn = self.record_ends_result()
+            except DPCapacityError as e:
+                cap = e.needed
+                continue
+            return self.d2h(np.empty(n, dtype), out.ptr), nq, nn
+
     def find_delim(self, d_buf: int, buf_len: int, buf_base: int, start: int, delim: int = 10) -> int:
         """First object offset >= start holding ``delim`` in the buffer, or -1."""
         pos = ctypes.c_int64(-1)
@@ -482,6 +547,10 @@ class ScanContext:
         if self._get_pool is not None:
             self._get_pool.shutdown(wait=True)
             self._get_pool = None
+        if self._dq is not None:
+            from . import _quote
+            h, self._dq = self._dq, None
+            _quote.check(_quote.load().dq_ctx_destroy(h))
         if self.handle:
             for b in list(self._bufs.values()) + list(self._pinned.values()):
                 b.free()

@@ -617,6 +617,60 @@ def line_index_object(co, begin: int = 0, end: Optional[int] = None, delim: int 
     return BlockedOffsets(low, table, merge.J0)
 
 
+def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: int = 34,
+                        max_devices: Optional[int] = None, part_bytes: int = 8 << 30) -> np.ndarray:
+    """Sorted uint64 offsets of the record ends of object bytes [begin, end): the '\\n' bytes outside quoted fields
+    (an even number of ``quote`` bytes between ``begin`` and the newline; include/dpquote.h).
+
+    The parts come from ``line_parts`` and run round-robin on the GPUs like a newline index.  A part does not know
+    whether it starts inside a quoted field, so it runs two launches on its resident bytes: a count-only one that
+    yields its number of quote bytes, and -- once the counts of every part before it are in, chained on the host
+    into the part's incoming state -- the emitting one.  The second read is of HBM, not of the storage."""
+    end = co.size if end is None else end
+    if end <= begin:
+        return np.zeros(0, np.uint64)
+    devs = devices(max_devices, co)
+    bounds = line_parts(begin, end, len(devs), part_bytes)
+    quotes = [0] * len(bounds)
+    counted = [threading.Event() for _ in bounds]
+    failed = threading.Event()
+    out = [None] * len(bounds)
+
+    def run(k: int):
+        lo, hi = bounds[k]
+        ctx = get_context(devs[k % len(devs)])
+        n = hi - lo
+        d = ctx.workspace("input", n + 64, placed=True)
+        dp = d.ptr + (lo & 15)
+        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
+        n_rec, quotes[k], _ = ctx.record_counts(dp, n, lo, lo, hi, quote=quote, carry=0)
+        counted[k].set()
+        for j in range(k):                               # parts before this one: on this worker done, on others
+            while not counted[j].wait(0.05):             # at least counted before they wait for anything
+                if failed.is_set():
+                    raise RuntimeError("record index: another part failed")
+        carry = sum(quotes[:k]) & 1
+        # the count under carry 0 bounds nothing under carry 1: size the output by the newlines only on a retry
+        out[k] = ctx.record_ends(dp, n, lo, lo, hi, quote=quote, carry=carry, u64=True,
+                                 cap=max(n_rec, 1) if carry == 0 else None)[0]
+
+    by_dev = {}
+    for k in range(len(bounds)):
+        by_dev.setdefault(k % len(devs), []).append(k)
+
+    def worker(ks):
+        try:
+            for k in ks:
+                run(k)
+        except BaseException:
+            failed.set()
+            raise
+
+    entries = sorted(by_dev)
+    run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    return out[0] if len(out) == 1 else np.concatenate(out)
+
+
 class PieceMerge:
     """Per-part outputs of a u16b / u8s newline index, in object order, as slices of the whole range's tables.
 

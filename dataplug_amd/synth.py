@@ -121,6 +121,44 @@ def csv_wide(size: int, seed: int = 0, max_note: int = 1500) -> np.ndarray:
     return out
 
 
+_NOTES = [b"checked", b"two lines\nhere", b"a, b and c", b'called ""the falls""', b"\n", b'""', b",", b"moved\n\nsee above",
+          b'""quoted"" start', b"ends with a break\n", b"plain text"]
+
+
+def csv_quoted(size: int, seed: int = 0) -> np.ndarray:
+    """``csv`` rows with an 11th column ``Note``: empty, plain, or RFC 4180 quoted text holding line breaks, commas
+    and escaped quotes (``""``).  Exactly ``size`` bytes, valid RFC 4180, deterministic, ends with a record end (the
+    last row's note is padded to fit)."""
+    head = CSV_HEADER[:-1] + b",Note\n"
+    if size < len(head) + 128:
+        raise ValueError(f"csv_quoted needs at least {len(head) + 128} bytes")
+    rng = np.random.default_rng(seed)
+    rows = [head]
+    total = len(head)
+    while True:
+        m = 4096
+        v = rng.integers(0, 60, (m, 6))
+        ci = rng.integers(0, len(_CITIES), m)
+        kind = rng.integers(0, 4, m)                      # 0 empty, 1 plain, 2-3 quoted
+        nfrag = rng.integers(1, 5, m)
+        frag = rng.integers(0, len(_NOTES), (m, 4))
+        for j in range(m):
+            base = b"%d,%d,%d,N,%d,%d,%d,W,%s," % (v[j, 0] % 50 + 25, v[j, 1], v[j, 2], v[j, 3] + 60, v[j, 4], v[j, 5],
+                                                   _CITIES[ci[j]])
+            if kind[j] == 0:
+                note = b""
+            elif kind[j] == 1:
+                note = b"plain note"
+            else:
+                note = b'"' + b" ".join(_NOTES[f] for f in frag[j, :nfrag[j]]) + b'"'
+            r = base + note + b"\n"
+            if size - total - len(r) < 128:               # the last row: a quoted note padded to the exact size
+                rows.append(base + b'"' + b"x" * (size - total - len(base) - 3) + b'"\n')
+                return np.frombuffer(b"".join(rows), np.uint8).copy()
+            rows.append(r)
+            total += len(r)
+
+
 VCF_HEADER = (b"##fileformat=VCFv4.2\n"
               b"##source=dataplug_amd.synth\n"
               b"##INFO=<ID=NS,Number=1,Type=Integer,Description=\"Samples With Data\">\n"

@@ -1,0 +1,76 @@
+/*
+ * dpquote.h — C ABI of libdpquote.so, the quote-aware CSV record index for the MI355X (gfx950).
+ *
+ * A library of its own next to libdpscan.so (dpscan.h): it shares the process, the HIP runtime and the
+ * caller's device memory with it, so every entry point takes raw device pointers and an opaque
+ * `void* stream` (= hipStream_t, e.g. the one dp_ctx_get_stream returns).  Status is returned as an int
+ * (DQ_OK = 0, the codes mirror DP_*); the message of the last failure on the calling thread is available
+ * from dq_last_error().  No C++ exception crosses this boundary.  Use one dq_ctx per host thread and
+ * stream; at most one dq_records_async is in flight per ctx.
+ *
+ * Semantics.  Over object bytes d[begin, end), a quote byte q and an incoming state carry (1 = "inside a
+ * quoted field at begin"): P(p) = (carry + #{x in [begin, p) : d[x] == q}) mod 2, and a byte d[p] == '\n'
+ * is a RECORD END iff P(p) == 0.  An escaped quote "" toggles twice, so the parity rule is exact for
+ * RFC 4180 input; for malformed input the parity rule is the definition.
+ *
+ * Reference interface this stands in for (CLOUDLAB-URV/dataplug @ 2025-07-11): the row boundaries that
+ * CSVSlice.get resolves byte by byte (formats/generic/csv.py:52-105).  The reference treats every '\n' as
+ * a row end there, which cuts RFC 4180 records whose quoted fields hold line breaks; this index is the
+ * set of '\n' that really end a record, as one sorted offset array.
+ */
+#ifndef DPQUOTE_H
+#define DPQUOTE_H
+
+#include <stdint.h>
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define DQ_OK 0
+#define DQ_ERR_INVALID 1   /* bad argument */
+#define DQ_ERR_HIP 2       /* a HIP runtime call failed (message in dq_last_error) */
+#define DQ_ERR_CAPACITY 3  /* output capacity too small; the required count is still returned */
+#define DQ_ERR_OVERFLOW 4  /* a uint32 offset would be >= 2^32 */
+#define DQ_ERR_TIMEOUT 5   /* an inter-workgroup wait hit its bound (results invalid) */
+
+typedef struct dq_ctx dq_ctx;
+
+#define DQ_ABI_VERSION 1
+int dq_abi_version(void);                                  /* returns DQ_ABI_VERSION of the build */
+const char* dq_last_error(void);                           /* thread-local message of the last failure */
+
+/* Binds `device` and `stream` (NULL: the device's default stream).  The ctx owns the tile ticket, the
+ * look-back descriptor array (grow-only device memory) and a pinned result block; it does not own the
+ * stream.  Fails with DQ_ERR_HIP (and a message) where there is no usable device. */
+int dq_ctx_create(int device, void* stream, dq_ctx** out);
+int dq_ctx_destroy(dq_ctx* ctx);                           /* waits for the stream first; NULL is a no-op */
+
+/*
+ * Record ends of object bytes [begin, end), enqueued on the ctx stream without waiting.
+ *   d_buf[0 .. buf_len) (device memory, any alignment) holds object bytes [buf_base, buf_base + buf_len);
+ *   buf_base <= begin <= end <= buf_base + buf_len.  quote: the quote byte (not '\n'); carry: 0 or 1.
+ *   d_out receives the ascending OBJECT offsets of the record ends, uint32 (out_u64 = 0) or uint64; at
+ *   most `cap` entries are written and nothing at or beyond d_out[cap].  cap = 0 with d_out = NULL is the
+ *   count-only call.  One pass over the bytes: every 64 KiB tile is read once, its incoming state and
+ *   output base come from a decoupled look-back over tile summaries.
+ */
+int dq_records_async(dq_ctx* ctx, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
+                     uint64_t end, uint32_t quote, uint32_t carry, void* d_out, int out_u64, uint64_t cap);
+/*
+ * Waits for the launch and returns its counts: *n_out record ends (the full count even beyond cap),
+ * *n_quotes bytes == quote, *n_newlines bytes == '\n' (kept or not) in [begin, end); each may be NULL.
+ *   DQ_ERR_CAPACITY: n_out > cap (the counts are still returned; the first cap entries are valid);
+ *   DQ_ERR_OVERFLOW: out_u64 = 0 and a record end lies at an offset >= 2^32;
+ *   DQ_ERR_TIMEOUT:  a look-back wait exceeded its 20 s bound; the kernel ended, the output is invalid.
+ */
+int dq_records_result(dq_ctx* ctx, uint64_t* n_out, uint64_t* n_quotes, uint64_t* n_newlines);
+
+/* Launch geometry (for tests/tuning): workgroups of the persistent grid, and bytes per tile. */
+int dq_geometry(dq_ctx* ctx, int* grid, int* tile_bytes);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DPQUOTE_H */

@@ -1,0 +1,173 @@
+"""libdpquote.so's record-end kernel through ScanContext.record_ends, bit-exact against the numpy model
+(tests/_quote_model.py): every length around the chunk / tile edges, contents that put quotes and newlines on those
+edges, both incoming states, unaligned ranges inside larger buffers, the output modes, capacity, and context reuse.
+With T, G = tile bytes, grid: the largest case hands more than one tile to a workgroup (a look-back deeper than one)."""
+import numpy as np
+import pytest
+
+from _quote_model import record_ends
+from dataplug_amd.scan import DPCapacityError, DPScanError, ScanContext
+
+pytestmark = pytest.mark.gpu
+
+ALPHABET = np.frombuffer(b'"\n,a', np.uint8)
+# mostly text, one quote and one newline in 32: records of ~32 bytes, quoted stretches across several of them
+SPARSE = np.frombuffer(b'"\n,,' + b"a" * 28, np.uint8)
+
+
+@pytest.fixture(scope="module")
+def geo(ctx):
+    t, g = ctx.quote_geometry()
+    assert t > 0 and t % 1024 == 0 and g > 0
+    return t, g
+
+
+def _run(ctx, buf: np.ndarray, lo: int, hi: int, buf_base: int = 0, carry: int = 0, u64: bool = True, mis: int = 0,
+         cap=None, quote: int = 34):
+    """record_ends of buffer bytes [lo, hi) -- object bytes [buf_base + lo, buf_base + hi) -- with the buffer placed
+    ``mis`` bytes past a 16-byte boundary; checked against the model."""
+    d = ctx.workspace("quote_in", len(buf) + 64)
+    if len(buf):
+        ctx.h2d(d.ptr + mis, buf)
+    got, nq, nn = ctx.record_ends(d.ptr + mis, len(buf), buf_base, buf_base + lo, buf_base + hi, quote=quote,
+                                  carry=carry, u64=u64, cap=cap)
+    exp, eq, en = record_ends(buf[lo:hi], base=buf_base + lo, quote=quote, carry=carry)
+    assert got.dtype == (np.uint64 if u64 else np.uint32)
+    assert (nq, nn) == (eq, en)
+    assert len(got) == len(exp) and np.array_equal(got.astype(np.uint64), exp)
+    return got
+
+
+def test_lengths_random_alphabet_both_states(ctx, geo):
+    t, _ = geo
+    rng = np.random.default_rng(1)
+    for n in (0, 1, 15, 16, 17, t - 1, t, t + 1, 2 * t + 5):
+        buf = ALPHABET[rng.integers(0, 4, n + 40)]
+        for carry in (0, 1):
+            _run(ctx, buf, 0, n, carry=carry)                                  # aligned, the buffer's head
+            _run(ctx, buf, 7, 7 + n, buf_base=1_000_003, carry=carry, mis=5)   # unaligned range, odd base
+
+
+def test_many_tiles_per_workgroup(ctx, geo):
+    t, g = geo
+    n = min(3 * g * t + 12345, 256 << 20)
+    assert n > g * t, "the ticket must hand some workgroup a second tile"
+    rng = np.random.default_rng(2)
+    buf = SPARSE[rng.integers(0, 32, n + 16, dtype=np.uint8)]
+    _run(ctx, buf, 3, 3 + n, buf_base=77, carry=1, mis=9)
+
+
+def test_uniform_contents(ctx, geo):
+    t, _ = geo
+    n = 2 * t + 5
+    for byte in (34, 10, 97):
+        buf = np.full(n, byte, np.uint8)
+        for carry in (0, 1):
+            got = _run(ctx, buf, 0, n, carry=carry)
+            assert len(got) == (n if byte == 10 and carry == 0 else 0)
+
+
+def test_quotes_and_newlines_on_the_edges(ctx, geo):
+    t, _ = geo
+    n = 2 * t + 100
+    for mis in (0, 11):
+        # a quote as the last byte of a tile, '\n' as the first byte of the next: suppressed, the one after "..." kept
+        buf = np.full(n, 97, np.uint8)
+        buf[t - 1], buf[t], buf[t + 5], buf[t + 7] = 34, 10, 34, 10
+        got = _run(ctx, buf, 0, n, mis=mis)
+        assert list(got) == [t + 7]
+        assert list(_run(ctx, buf, 0, n, carry=1, mis=mis)) == [t]
+        # "" across a 16-byte chunk edge, a wave-row edge (1 KiB), a wave edge (16 KiB) and a tile edge, a newline
+        # after each: the pair toggles twice, every newline is kept; under carry 1 none is
+        buf = np.full(n, 97, np.uint8)
+        edges = (16, 1024, 16384, t, t + 16384, 2 * t)
+        for e in edges:
+            buf[e - 1], buf[e], buf[e + 3] = 34, 34, 10
+        assert list(_run(ctx, buf, 0, n, mis=mis)) == [e + 3 for e in edges]
+        assert len(_run(ctx, buf, 0, n, carry=1, mis=mis)) == 0
+        # the same pairs shifted so that they straddle the kernel's edges when the range starts mid-chunk
+        assert len(_run(ctx, buf, 13, n - 3, buf_base=29, mis=mis)) == len(edges)
+
+
+def test_one_quote_suppresses_everything_after_it(ctx, geo):
+    t, _ = geo
+    n = 3 * t + 17
+    buf = np.full(n, 10, np.uint8)
+    buf[0] = 34
+    assert len(_run(ctx, buf, 0, n)) == 0
+    assert len(_run(ctx, buf, 0, n, carry=1)) == n - 1
+    assert len(_run(ctx, buf, 1, n)) == n - 1                       # the quote outside the range does not count
+    assert len(_run(ctx, buf, 0, n, quote=39)) == n - 1             # another quote byte: '"' is plain text
+
+
+def test_uint32_output_and_overflow(ctx, geo):
+    t, _ = geo
+    rng = np.random.default_rng(3)
+    buf = ALPHABET[rng.integers(0, 4, t + 333)]
+    a = _run(ctx, buf, 0, len(buf), buf_base=12345, u64=True)
+    b = _run(ctx, buf, 0, len(buf), buf_base=12345, u64=False)
+    assert np.array_equal(a, b.astype(np.uint64))
+    base = (1 << 32) - 100                                          # the range crosses 2^32
+    buf = np.full(300, 10, np.uint8)
+    with pytest.raises(OverflowError):
+        _run(ctx, buf, 0, 300, buf_base=base, u64=False)
+    got = _run(ctx, buf, 0, 300, buf_base=base, u64=True)
+    assert int(got[-1]) == base + 299 and int(got[0]) == base
+    _run(ctx, buf, 0, 100, buf_base=base, u64=False)                # wholly below 2^32: fine as uint32
+
+
+def test_capacity_and_count_only(ctx, geo):
+    t, _ = geo
+    rng = np.random.default_rng(4)
+    buf = ALPHABET[rng.integers(0, 4, t + 4096)]
+    exp, eq, en = record_ends(buf, base=50)
+    assert len(exp) > 1000
+    d = ctx.workspace("quote_in", len(buf) + 64)
+    ctx.h2d(d.ptr, buf)
+    assert ctx.record_counts(d.ptr, len(buf), 50, 50, 50 + len(buf)) == (len(exp), eq, en)
+    assert ctx.record_counts(d.ptr, len(buf), 50, 50, 50 + len(buf), carry=1)[0] == \
+        len(record_ends(buf, base=50, carry=1)[0])
+    cap = 777
+    canary = np.full(len(exp) + 64, 0xEEEEEEEEEEEEEEEE, np.uint64)
+    out = ctx.workspace("quote_canary", canary.nbytes)
+    ctx.h2d(out.ptr, canary)
+    ctx.record_ends_async(d.ptr, len(buf), 50, 50, 50 + len(buf), 34, 0, out.ptr, True, cap)
+    with pytest.raises(DPCapacityError) as ei:
+        ctx.record_ends_result()
+    assert ei.value.needed == len(exp) and (ei.value.n_quotes, ei.value.n_newlines) == (eq, en)
+    back = ctx.d2h(np.empty_like(canary), out.ptr)
+    assert np.array_equal(back[:cap], exp[:cap])
+    assert np.array_equal(back[cap:], canary[cap:]), "written at or beyond cap"
+    got, _, _ = ctx.record_ends(d.ptr, len(buf), 50, 50, 50 + len(buf), cap=1)   # the wrapper retries with the count
+    assert np.array_equal(got, exp)
+
+
+def test_bad_arguments_are_refused(ctx):
+    d = ctx.workspace("quote_in", 4096)
+    for kw in ({"quote": 10}, {"quote": 300}, {"carry": 2}):
+        with pytest.raises(DPScanError):
+            ctx.record_ends(d.ptr, 100, 0, 0, 100, **kw)
+    with pytest.raises(DPScanError):
+        ctx.record_ends(d.ptr, 100, 10, 5, 50)                      # begins before the buffer
+    with pytest.raises(DPScanError):
+        ctx.record_ends(d.ptr, 100, 10, 20, 111)                    # ends past it
+    assert len(ctx.record_ends(d.ptr, 100, 10, 60, 60)[0]) == 0     # empty range
+
+
+def test_reuse_of_one_context_and_two_contexts(ctx, geo):
+    t, _ = geo
+    rng = np.random.default_rng(5)
+    big = ALPHABET[rng.integers(0, 4, 5 * t + 3)]
+    small = ALPHABET[rng.integers(0, 4, t + 9)]
+    first = _run(ctx, big, 0, len(big))
+    _run(ctx, small, 0, len(small), carry=1)                        # fewer tiles: the earlier descriptors are stale
+    again = _run(ctx, big, 0, len(big))
+    assert np.array_equal(first, again)
+    other = ScanContext(0)
+    try:
+        assert np.array_equal(_run(other, big, 0, len(big)), first)
+        assert np.array_equal(_run(ctx, big, 0, len(big)), first)
+        assert np.array_equal(_run(other, small, 2, len(small), carry=1, mis=3),
+                              record_ends(small[2:], base=2, carry=1)[0])
+    finally:
+        other.close()

@@ -1,0 +1,143 @@
+"""Device-resident rate of the quote-aware record index (libdpquote.so), for DESIGN.md and the README row.
+
+    python tools/quote_rate.py [--gib G | --mib M] [--reps R] [--block-mib B]
+
+A ``synth.csv_quoted`` block (B MiB, RFC 4180, ends at a record end) is copied end to end into one device buffer of
+the asked size (whole blocks, so the expected record ends are the block's, shifted).  On that one buffer, in one
+process, alternating launch by launch after a warm-up of each:
+* ``dq_records_async`` (uint64 output), HIP events on the context stream around the whole call: the per-launch
+  zeroing of the descriptors, the kernel and the 64-byte result copy;
+* ``dp_stream_read``, the read-only calibration kernel, and ``dp_delim_index`` (uint64), the newline index, each timed
+  by the library's own HIP events around its kernels (dp_timing_enable).
+Prints one JSON line: the three times and GiB/s (input bytes over time), the ratio of the record index's rate to each
+of the other two, and whether the last record-index output equals the numpy model.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from dataplug_amd import synth  # noqa: E402
+from dataplug_amd.scan import get_context  # noqa: E402
+
+GiB = float(1 << 30)
+
+
+class Events:
+    """A pair of HIP events on one stream (the runtime libdpscan already loaded)."""
+
+    def __init__(self, stream: int):
+        self.hip = ctypes.CDLL(os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so"))
+        self.stream = ctypes.c_void_p(stream)
+        self.a, self.b = ctypes.c_void_p(), ctypes.c_void_p()
+        for e in (self.a, self.b):
+            self._ok(self.hip.hipEventCreate(ctypes.byref(e)))
+
+    @staticmethod
+    def _ok(rc):
+        if rc:
+            raise RuntimeError(f"HIP event call failed: {rc}")
+
+    def start(self):
+        self._ok(self.hip.hipEventRecord(self.a, self.stream))
+
+    def stop_ms(self) -> float:
+        self._ok(self.hip.hipEventRecord(self.b, self.stream))
+        self._ok(self.hip.hipEventSynchronize(self.b))
+        ms = ctypes.c_float(0)
+        self._ok(self.hip.hipEventElapsedTime(ctypes.byref(ms), self.a, self.b))
+        return float(ms.value)
+
+
+def model_ends(d: np.ndarray) -> np.ndarray:
+    par = np.cumsum(d == 34, dtype=np.uint8) & np.uint8(1)
+    return np.flatnonzero((d == 10) & (par == 0)).astype(np.uint64)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=4.0)
+    ap.add_argument("--mib", type=float, default=None, help="buffer size in MiB instead of --gib")
+    ap.add_argument("--block-mib", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=12)
+    args = ap.parse_args()
+    assert args.reps >= 10, "at least 10 timed launches each"
+    want = int((args.mib * (1 << 20)) if args.mib is not None else (args.gib * (1 << 30)))
+    block = synth.csv_quoted(min(args.block_mib << 20, want), seed=21)
+    copies = max(1, want // len(block))
+    n = copies * len(block)
+    ends = model_ends(block)
+    assert int(np.count_nonzero(block == 34)) % 2 == 0 and int(ends[-1]) == len(block) - 1
+    exp = np.concatenate([ends + np.uint64(i * len(block)) for i in range(copies)])
+
+    ctx = get_context(0)
+    d = ctx.workspace("quote_rate_in", n + 64, placed=True)
+    for i in range(copies):
+        ctx.h2d(d.ptr + i * len(block), block)
+    cap = len(exp) + 1024
+    nl_cap = copies * int(np.count_nonzero(block == 10)) + 1024
+    out = ctx.workspace("quote_rate_out", 8 * max(cap, nl_cap))
+    ev = Events(ctx.stream)
+    n16 = n // 16 * 16
+
+    def quote():
+        ev.start()
+        ctx.record_ends_async(d.ptr, n, 0, 0, n, 34, 0, out.ptr, True, cap)
+        ms = ev.stop_ms()
+        return ms, ctx.record_ends_result()
+
+    def timed(fn):
+        ctx.timing_read()
+        fn()
+        ms, k = ctx.timing_read()
+        assert k >= 1
+        return ms
+
+    def read():
+        return timed(lambda: ctx.stream_read(d.ptr, n16))
+
+    def delim():
+        def go():
+            ctx.delim_index_async(d.ptr, n, 0, 0, n, 10, 1, 0, out.ptr, True, nl_cap)
+            ctx.delim_result()
+        return timed(go)
+
+    ctx.timing(True)
+    for _ in range(2):                                              # warm-up of every kernel at this size
+        quote(), read(), delim()
+    tq, tr, td = [], [], []
+    for _ in range(args.reps):
+        tr.append(read())
+        td.append(delim())
+        ms, (n_out, n_quotes, n_newlines) = quote()                 # last: its output is the one verified
+        tq.append(ms)
+    ctx.timing(False)
+    got = ctx.d2h(np.empty(n_out, np.uint64), out.ptr)
+    ok = bool(n_out == len(exp) and np.array_equal(got, exp) and n_quotes == copies * int(np.count_nonzero(block == 34))
+              and n_newlines == copies * int(np.count_nonzero(block == 10)))
+
+    def rate(ts, nbytes):
+        return round(nbytes / (float(np.median(ts)) / 1e3) / GiB, 1)
+
+    rq, rr, rd = rate(tq, n), rate(tr, n16), rate(td, n)
+    print(json.dumps({
+        "bytes": n, "records": int(n_out), "newlines": int(n_newlines), "quotes": int(n_quotes), "reps": args.reps,
+        "tile_bytes_grid": list(ctx.quote_geometry()),
+        "record_index_ms": [round(float(np.median(tq)), 3), round(min(tq), 3), round(max(tq), 3)],
+        "stream_read_ms": [round(float(np.median(tr)), 3), round(min(tr), 3), round(max(tr), 3)],
+        "newline_index_ms": [round(float(np.median(td)), 3), round(min(td), 3), round(max(td), 3)],
+        "record_index_GiB_per_s": rq, "stream_read_GiB_per_s": rr, "newline_index_u64_GiB_per_s": rd,
+        "ratio_to_stream_read": round(rq / rr, 3), "ratio_to_newline_index": round(rq / rd, 3),
+        "newline_index_form": ctx.last_delim_form(), "verified": ok}), flush=True)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
