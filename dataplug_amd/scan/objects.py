@@ -658,16 +658,25 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
     for k in range(len(bounds)):
         by_dev.setdefault(k % len(devs), []).append(k)
 
+    errors = []
+
     def worker(ks):
         try:
             for k in ks:
                 run(k)
-        except BaseException:
-            failed.set()
+        except BaseException as e:
+            errors.append(e)                             # before the event: the first entry is the cause, the parts
+            failed.set()                                 # it releases add their "another part failed" behind it
             raise
 
     entries = sorted(by_dev)
-    run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    try:
+        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    except BaseException as e:
+        # the caller gets the failure itself, not the error of a released waiter whose worker happens to come first
+        if errors and errors[0] is not e:
+            raise errors[0] from None
+        raise
     return out[0] if len(out) == 1 else np.concatenate(out)
 
 

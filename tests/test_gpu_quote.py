@@ -1,12 +1,26 @@
 """libdpquote.so's record-end kernel through ScanContext.record_ends, bit-exact against the numpy model
 (tests/_quote_model.py): every length around the chunk / tile edges, contents that put quotes and newlines on those
 edges, both incoming states, unaligned ranges inside larger buffers, the output modes, capacity, and context reuse.
-With T, G = tile bytes, grid: the largest case hands more than one tile to a workgroup (a look-back deeper than one)."""
+With T, G = tile bytes, grid: the largest case hands more than one tile to a workgroup (a look-back deeper than one).
+
+The last two tests pin the lane-exact model of the kernel (tools/emulate_quote.py) to the hardware: every quote byte
+against every data byte in every chunk position (v_perm_b32 and the signed v_dot4_i32_i8 as the model reads them), and
+the kernel's offsets, counts and capacity error equal to the model's.  Nothing here tries to steer how the hardware
+schedules workgroups: which descriptors a look-back finds published is left to timing on a GPU, so the look-back's
+walks across 64-descriptor windows are shown correct on the CPU only, by tests/test_quote_model.py over schedules the
+hardware cannot be made to produce on demand."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
+from _quote_cases import every_value_every_position, one_lane_16
 from _quote_model import record_ends
 from dataplug_amd.scan import DPCapacityError, DPScanError, ScanContext
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import emulate_quote as emu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -171,3 +185,63 @@ def test_reuse_of_one_context_and_two_contexts(ctx, geo):
                               record_ends(small[2:], base=2, carry=1)[0])
     finally:
         other.close()
+
+
+# ------------------------------------------------------------------------------------------ the lane-exact model
+def _run_both(ctx, buf, lo, hi, **kw):
+    """_run (the kernel against the definition), then the lane model of the same launch against the kernel."""
+    got = _run(ctx, buf, lo, hi, **kw)
+    mis, base = kw.get("mis", 0), kw.get("buf_base", 0)
+    addr = ctx.workspace("quote_in", len(buf) + 64).ptr + mis
+    off, n_out, nq, nn, err = emu.run(buf, dev_addr=addr, buf_base=base, begin=base + lo, end=base + hi,
+                                      quote=kw.get("quote", 34), carry=kw.get("carry", 0), u64=kw.get("u64", True))
+    assert err == 0 and n_out == len(got) and off.dtype == got.dtype and np.array_equal(off, got)
+    assert (nq, nn) == record_ends(buf[lo:hi], quote=kw.get("quote", 34))[1:]
+    return got
+
+
+def test_every_quote_byte_against_every_data_byte(ctx):
+    data = every_value_every_position(4096)
+    mis, lo = 5, 7
+    shift = (mis + lo) % 16                              # chunk position of the range's first byte
+    seen = np.zeros((256, 16), bool)
+    seen[data, (shift + np.arange(4096)) % 16] = True
+    assert seen.all(), "every byte value in every position of a 16-byte chunk"
+    buf = np.empty(4096 + 40, np.uint8)
+    buf[lo:lo + 4096] = data
+    for quote in range(256):
+        if quote == 10:
+            continue
+        pad = np.resize(np.array([quote, 10], np.uint8), 40)         # the bytes around the range: quotes and newlines
+        buf[:lo], buf[lo + 4096:] = pad[:lo], pad[lo:]
+        for carry in (0, 1):
+            _run_both(ctx, buf, lo, lo + 4096, buf_base=1_000_003, carry=carry, mis=mis, quote=quote)
+
+
+def test_kernel_equals_lane_model(ctx, geo):
+    t, _ = geo
+    assert t == emu.TILE_BYTES
+    rng = np.random.default_rng(6)
+    for n in (t - 1, t + 1, 3 * t + 17):
+        for name, buf in (("alphabet", ALPHABET[rng.integers(0, 4, n + 40)]), ("one_lane_16", one_lane_16(n + 40, n))):
+            for mis in (0, 11):
+                for carry in (0, 1):
+                    for u64 in (True, False):
+                        _run_both(ctx, buf, 7, 7 + n, buf_base=29, carry=carry, u64=u64, mis=mis)
+    # a capacity below the count: the stores below cap, the count and the capacity error as the model has them
+    buf = ALPHABET[rng.integers(0, 4, t + 4096)]
+    d = ctx.workspace("quote_in", len(buf) + 64)
+    ctx.h2d(d.ptr + 11, buf)
+    for u64 in (True, False):
+        cap = 777
+        off, n_out, nq, nn, err = emu.run(buf, dev_addr=d.ptr + 11, buf_base=50, carry=1, u64=u64, cap=cap)
+        assert err == emu.ERR_CAPACITY and n_out > cap and len(off) == cap
+        canary = np.full(n_out + 64, 0xEEEEEEEE, off.dtype)
+        out = ctx.workspace("quote_canary", canary.nbytes)
+        ctx.h2d(out.ptr, canary)
+        ctx.record_ends_async(d.ptr + 11, len(buf), 50, 50, 50 + len(buf), 34, 1, out.ptr, u64, cap)
+        with pytest.raises(DPCapacityError) as ei:
+            ctx.record_ends_result()
+        assert (ei.value.needed, ei.value.n_quotes, ei.value.n_newlines) == (n_out, nq, nn)
+        back = ctx.d2h(np.empty_like(canary), out.ptr)
+        assert np.array_equal(back[:cap], off) and np.array_equal(back[cap:], canary[cap:])

@@ -1,7 +1,8 @@
 """The quote-aware record index without a GPU: libdpquote.so's ABI, ISA-guard stamp and loader refusal, the numpy
 model against Python's csv module, and the record partition strategies over an in-memory store with a record index
 written from the model (the scan is replaced by a stub, so this checks host logic only; tests/test_gpu_quote*.py run
-the kernel)."""
+the kernel).  The last section runs scan.objects.record_index_object itself -- the per-part counts, the carry chain,
+the capacity choice and the release of waiting parts after a failure -- over a numpy-backed fake of the device layer."""
 import csv as pycsv
 import ctypes
 import io
@@ -10,6 +11,8 @@ import os
 import pickle
 import re
 import shutil
+import threading
+import time
 
 import numpy as np
 import pytest
@@ -265,3 +268,158 @@ def test_missing_record_index_is_a_key_error_and_default_preprocess_is_unchanged
         co.partition(fcsv.partition_records_chunk_size, chunk_size=1000)
     with pytest.raises(ValueError):
         fcsv.preprocess_csv(co, line_index=False, quotechar="\n")
+
+
+# ------------------------------------------------------------------------------------------------ record_index_object
+class FakeBuffer:
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+
+class FakeContext:
+    """What record_index_object uses of a ScanContext, over numpy memory: workspace, record_counts and record_ends,
+    the two scans from the model, honouring carry and cap (a too small cap costs a second launch, as on the GPU)."""
+    BASE = 1 << 20                                       # device address of the context's memory, 16-byte aligned
+
+    def __init__(self, layer):
+        self.layer = layer
+        self.mem = np.zeros(0, np.uint8)
+
+    def workspace(self, name, nbytes, placed=False):
+        assert name == "input"
+        if len(self.mem) < nbytes:
+            self.mem = np.zeros(nbytes, np.uint8)
+        return FakeBuffer(self.BASE)
+
+    def _bytes(self, d_buf, buf_len, buf_base, begin, end):
+        assert buf_base <= begin <= end <= buf_base + buf_len and d_buf + buf_len <= self.BASE + len(self.mem)
+        a = d_buf - self.BASE + (begin - buf_base)
+        return self.mem[a:a + end - begin]
+
+    def record_counts(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0):
+        self.layer.note("counts", begin, end, carry, 0)
+        if self.layer.fail_counts_at == begin:
+            raise RuntimeError("fake: record_counts failed")
+        ends, nq, nn = record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
+        return len(ends), nq, nn
+
+    def record_ends(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, u64=True, cap=None):
+        assert u64
+        ends, nq, nn = record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
+        if cap is None:
+            cap = (end - begin) // 16 + 1024
+        self.layer.note("ends", begin, end, carry, cap)
+        if len(ends) > cap:                              # DPCapacityError, then the launch sized by the count
+            self.layer.note("ends", begin, end, carry, len(ends))
+        return ends, nq, nn
+
+
+class FakeDevices:
+    """scan.objects' device layer replaced: get_context (one context per thread and device, like the real one),
+    fetch_to_device (the object's bytes into the context's numpy memory) and devices."""
+
+    def __init__(self, monkeypatch, devs):
+        self.tls = threading.local()
+        self.lock = threading.Lock()
+        self.calls = []
+        self.fail_counts_at = None
+        monkeypatch.setattr(scan_objects, "get_context", self.get_context)
+        monkeypatch.setattr(scan_objects, "fetch_to_device", self.fetch_to_device)
+        monkeypatch.setattr(scan_objects, "devices", lambda max_devices=None, co=None: list(devs))
+
+    def note(self, *call):
+        with self.lock:
+            self.calls.append(call)
+
+    def get_context(self, device=0, slot=0):
+        ctxs = self.tls.__dict__.setdefault("ctxs", {})
+        if device not in ctxs:
+            ctxs[device] = FakeContext(self)
+        return ctxs[device]
+
+    def fetch_to_device(self, ctx, storage, bucket, key, lo, hi, d_ptr, **kw):
+        raw = storage.get_object(Bucket=bucket, Key=key, Range=f"bytes={lo}-{hi - 1}")["Body"].read()
+        assert len(raw) == hi - lo and d_ptr % 16 == lo % 16
+        a = d_ptr - ctx.BASE
+        ctx.mem[a:a + hi - lo] = np.frombuffer(raw, np.uint8)
+
+
+CHAIN_BYTES, CHAIN_PART = (1 << 18) + 77, 1 << 14
+
+
+@pytest.fixture(scope="module")
+def chain_data():
+    data = synth.csv_quoted(CHAIN_BYTES, seed=11)
+    return data, record_ends(data)[0]
+
+
+def _check_chain(fake, data, begin, end, got, min_parts=16, min_inside=3):
+    """The result is the definition over [begin, end); every launch had the parity of the quotes before its part."""
+    assert got.dtype == np.uint64 and np.array_equal(got, record_ends(data[begin:end], base=begin)[0])
+    parts = scan_objects.line_parts(begin, end, 1, CHAIN_PART)
+    inside = [int(np.count_nonzero(data[begin:lo] == 34)) & 1 for lo, _ in parts]
+    assert len(parts) >= min_parts and sum(inside) >= min_inside
+    counts = sorted(c[1:] for c in fake.calls if c[0] == "counts")
+    assert counts == [(lo, hi, 0, 0) for lo, hi in parts]               # one count-only launch per part, carry 0
+    emits = [c for c in fake.calls if c[0] == "ends"]
+    first = {}
+    for _, lo, hi, carry, cap in emits:
+        assert carry == inside[parts.index((lo, hi))], (lo, carry)
+        first.setdefault((lo, hi), cap)
+    assert sorted(first) == parts
+    for (lo, hi), cap in first.items():                  # sized by the count-only launch only where that is a bound
+        n0 = len(record_ends(data[lo:hi])[0])
+        assert cap == (max(n0, 1) if not inside[parts.index((lo, hi))] else (hi - lo) // 16 + 1024)
+    assert len(emits) == len(parts) + sum(1 for (lo, hi), cap in first.items()
+                                          if len(record_ends(data[lo:hi], carry=inside[parts.index((lo, hi))])[0]) > cap)
+
+
+@pytest.mark.parametrize("devs", [[0], [0, 0, 0]])
+def test_record_index_object_chains_the_parts(monkeypatch, chain_data, devs):
+    data, model = chain_data
+    fake = FakeDevices(monkeypatch, devs)
+    co = _co(data.tobytes(), "chain.csv", _mem(f"quote_cpu_chain{len(devs)}"))
+    got = scan_objects.record_index_object(co, part_bytes=CHAIN_PART)
+    assert np.array_equal(got, model)
+    assert scan_objects.line_parts(0, len(data), len(devs), CHAIN_PART) == scan_objects.line_parts(0, len(data), 1, CHAIN_PART)
+    _check_chain(fake, data, 0, len(data), got)
+    # a sub-range that starts at a record boundary (not at a part boundary of the whole object) and ends mid-record
+    fake.calls.clear()
+    begin, end = int(model[len(model) // 7]) + 1, len(data) - 1234
+    assert begin % CHAIN_PART and data[end - 1] != 10
+    _check_chain(fake, data, begin, end, scan_objects.record_index_object(co, begin, end, part_bytes=CHAIN_PART),
+                 min_parts=12, min_inside=1)
+    assert len(scan_objects.record_index_object(co, 500, 500)) == 0
+
+
+def test_record_index_object_releases_the_waiting_parts_when_one_fails(monkeypatch, chain_data):
+    data, model = chain_data
+    fake = FakeDevices(monkeypatch, [0, 0, 0])
+    co = _co(data.tobytes(), "fail.csv", _mem("quote_cpu_fail"))
+    t0 = time.perf_counter()
+    assert np.array_equal(scan_objects.record_index_object(co, part_bytes=CHAIN_PART), model)
+    healthy = time.perf_counter() - t0
+    parts = scan_objects.line_parts(0, len(data), 3, CHAIN_PART)
+    result = {}
+
+    def call():
+        try:
+            result["value"] = scan_objects.record_index_object(co, part_bytes=CHAIN_PART)
+        except BaseException as e:
+            result["error"] = e
+
+    fake.fail_counts_at = parts[1][0]                    # part 1 never publishes its count: parts 2.. wait for it
+    th = threading.Thread(target=call, daemon=True)
+    th.start()
+    # a guard against a hang, not a speed: the healthy call above takes tens of milliseconds here, a released waiter
+    # notices the failure at its next 50 ms poll; 200 times the healthy run and at least 20 s leaves a loaded machine
+    # two orders of magnitude, and a hang still fails the test instead of stalling the suite
+    th.join(max(20.0, 200 * healthy))
+    assert not th.is_alive(), "record_index_object hangs when a part fails"
+    assert "value" not in result and isinstance(result["error"], RuntimeError)
+    assert "fake: record_counts failed" in str(result["error"]), "the caller must see the cause, not a released waiter"
+    fake.fail_counts_at = None
+    scan_objects.release_workers()                       # the workers are idle again: this returns
+    fake.calls.clear()
+    assert np.array_equal(scan_objects.record_index_object(co, part_bytes=CHAIN_PART), model)
+    _check_chain(fake, data, 0, len(data), model)
