@@ -13,6 +13,11 @@
 // depends on a tile that a running or finished workgroup owns: no co-residency assumption); every inter-workgroup
 // wait is bounded in time (20 s of the realtime counter, DQ_ERR_TIMEOUT, the waiters are released); the ticket, the
 // result words and the descriptors are zeroed per launch on the stream; outputs are ordinary vector stores.
+//
+// Three output forms of the one kernel template: uint32 and uint64 object offsets (tiles start at the 16-byte boundary
+// at or below the range's first byte), and the blocked form u16b (dq_records_blocked_async): tiles lie on the object's
+// 64 KiB grid, so a record end's uint16 low word is its position in the tile and the block table entry of a tile is
+// the exclusive base its look-back resolves anyway.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,14 +68,16 @@ __device__ __forceinline__ bool wait_expired(uint32_t spins, uint64_t& t0) {
 }
 
 struct QuoteArgs {
-  const uint8_t* base;         // 16-byte aligned; coordinates below are relative to it
-  uint64_t lo, hi;             // the bytes to scan: [lo, hi), lo in 0..15
+  const uint8_t* base;         // 16-byte aligned; coordinates below are relative to it (blocked form: it may lie
+                               // before the allocation; only chunks that hold a byte of [lo, hi) are loaded)
+  uint64_t lo, hi;             // the bytes to scan: [lo, hi), lo in 0..15 (blocked form: 0..65535)
   uint64_t obj0;               // object offset of coordinate 0 (mod 2^64: only coordinates >= lo are emitted)
   uint64_t ntiles;
   uint32_t key_q, key_nl;      // match4 keys of the quote byte and of '\n'
   uint32_t carry;
   void* out;
   uint64_t cap;
+  unsigned long long* table;   // blocked form: ntiles entries, the record ends of the launch before each tile
   unsigned long long* ctrl;    // kCtrlWords control words, then ntiles descriptors
 };
 
@@ -89,7 +96,8 @@ __device__ __forceinline__ uint32_t mask16(const uint4& v, uint32_t key) {
   const uint32_t hi = ((uint32_t)d3 << 4) + (uint32_t)d2;
   return ((hi << 8) + lo) & 0xFFFFu;
 }
-// the bytes of the 16-byte chunk at coordinate x that lie in [lo, hi), as 16 bits (the chunk overlaps the range)
+// the bytes of the 16-byte chunk at coordinate x that lie in [lo, hi), as 16 bits (the chunk overlaps the range:
+// x < hi and x + 16 > lo, whatever lo is)
 __device__ __forceinline__ uint32_t valid16(uint64_t x, uint64_t lo, uint64_t hi) {
   const uint32_t a = lo > x ? (uint32_t)(lo - x) : 0u;              // < 16
   const uint32_t b = hi - x < 16u ? (uint32_t)(hi - x) : 16u;       // 1..16
@@ -185,10 +193,12 @@ __device__ __forceinline__ bool look_back(const QuoteArgs& A, uint64_t tile, int
   }
 }
 
+// OUT64: 0 uint32 offsets, 1 uint64 offsets, 2 uint16 low words + the 64 KiB block table (tiles on the object's grid)
 template <int OUT64>
 __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
   __shared__ Shared S;
-  using OutT = typename std::conditional<OUT64 == 1, uint64_t, uint32_t>::type;
+  using OutT = typename std::conditional<OUT64 == 1, uint64_t,
+                                         typename std::conditional<OUT64 == 2, uint16_t, uint32_t>::type>::type;
   OutT* const out = reinterpret_cast<OutT*>(A.out);
   unsigned long long* const desc = A.ctrl + kCtrlWords;
   const int lane = threadIdx.x & (kWave - 1);
@@ -215,6 +225,7 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
         const uint64_t x = x0 + (uint64_t)(h + r) * kRowBytes;
         v[r] = make_uint4(0u, 0u, 0u, 0u);
         ok[r] = 0u;
+        // (blocked form: the chunks of a first tile's leading rows and waves lie wholly below lo and stay zero)
         if (x < A.hi && x + 16u > A.lo) {          // the chunk holds a byte of [lo, hi): inside the buffer's pages
           v[r] = *reinterpret_cast<const uint4*>(A.base + x);
           ok[r] = valid16(x, A.lo, A.hi);
@@ -277,6 +288,7 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
         S.state_in = state_in;
         S.base = base;
         S.abort = ok ? 0u : 1u;
+        if (OUT64 == 2) A.table[tile] = base;      // the record ends before the tile: its entry of the block table
         if (tq) atomicAdd(A.ctrl + kCtrlQuotes, (unsigned long long)tq);
         if (tn) atomicAdd(A.ctrl + kCtrlNewlines, (unsigned long long)tn);
         if (tile + 1 == A.ntiles) A.ctrl[kCtrlOut] = incl;
@@ -317,7 +329,9 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
         const uint64_t o = off + (uint32_t)__builtin_ctz(kept);
         kept &= kept - 1u;
         if (OUT64 == 0 && (o >> 32)) overflow = 1u;
-        else if (i < A.cap) out[i] = (OutT)o;
+        else if (OUT64 == 2) {                     // obj0 is a multiple of 64 KiB: the low word of the offset is the
+          if (i < A.cap) out[i] = (OutT)(uint32_t)o;   // byte's position in its tile (32-bit arithmetic is enough)
+        } else if (i < A.cap) out[i] = (OutT)o;
         ++i;
       }
       wbase += total;
@@ -374,6 +388,9 @@ int dq_ctx_create(int device, void* stream, dq_ctx** out) {
   int occ1 = 0;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, quote_kernel<1>, kThreads, 0));
   if (occ1 < occ) occ = occ1;
+  int occ2 = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, quote_kernel<2>, kThreads, 0));
+  if (occ2 < occ) occ = occ2;
   if (occ < 1) return fail(DQ_ERR_HIP, "quote_kernel: no resident workgroup per CU");
   if (occ > kMaxBlocksPerCU) occ = kMaxBlocksPerCU;
   dq_ctx* c = new dq_ctx();
@@ -400,8 +417,11 @@ int dq_ctx_destroy(dq_ctx* c) {
   return DQ_OK;
 }
 
-int dq_records_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
-                     uint64_t end, uint32_t quote, uint32_t carry, void* d_out, int out_u64, uint64_t cap) {
+// The launch behind both entry points.  form: 0 uint32, 1 uint64 (coordinate 0 = the 16-byte boundary at or below
+// the device address of `begin`), 2 blocked (coordinate 0 = object offset begin & ~0xFFFF, d_table required).
+static int records_launch(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
+                          uint64_t end, uint32_t quote, uint32_t carry, void* d_out, int form, uint64_t cap,
+                          uint64_t* d_table, uint64_t table_cap) {
   if (!c) return fail(DQ_ERR_INVALID, "null ctx");
   if (c->in_flight) return fail(DQ_ERR_INVALID, "a launch is in flight: collect it with dq_records_result");
   if (begin > end || begin < buf_base || end - buf_base > buf_len)
@@ -410,15 +430,32 @@ int dq_records_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t
   if (quote > 255u || quote == 10u) return fail(DQ_ERR_INVALID, "quote must be a byte other than '\\n'");
   if (carry > 1u) return fail(DQ_ERR_INVALID, "carry must be 0 or 1");
   if (cap && !d_out) return fail(DQ_ERR_INVALID, "null output with cap > 0");
-  if (out_u64 != 0 && out_u64 != 1) return fail(DQ_ERR_INVALID, "out_u64 must be 0 or 1");
-  if (cap && ((uintptr_t)d_out & (out_u64 ? 7u : 3u))) return fail(DQ_ERR_INVALID, "misaligned output");
-  HIPCHK(hipSetDevice(c->device));
+  if (form < 0 || form > 2) return fail(DQ_ERR_INVALID, "out_u64 must be 0 or 1");
+  if (cap && ((uintptr_t)d_out & (form == 1 ? 7u : form == 2 ? 1u : 3u)))
+    return fail(DQ_ERR_INVALID, "misaligned output");
 
   const uint64_t len = end - begin;
   const uintptr_t p = (uintptr_t)d_buf + (uintptr_t)(begin - buf_base);
-  const uint64_t shift = len ? (uint64_t)(p & 15u) : 0u;
-  const uint64_t ntiles = len ? (shift + len + kTileBytes - 1) / kTileBytes : 0u;
+  uint64_t shift, ntiles, obj0;
+  if (form == 2) {
+    // tiles on the object's 64 KiB grid: coordinate 0 may lie before the allocation (never dereferenced there)
+    if (len && ((p ^ begin) & 15u))
+      return fail(DQ_ERR_INVALID, "blocked form: the device address of `begin` must be congruent to begin mod 16");
+    if ((uintptr_t)d_table & 7u) return fail(DQ_ERR_INVALID, "misaligned block table");
+    shift = len ? (begin & 0xFFFFu) : 0u;
+    obj0 = begin & ~(uint64_t)0xFFFFu;
+    ntiles = len ? ((end - 1) >> 16) - (begin >> 16) + 1 : 0u;
+    if (ntiles && !d_table) return fail(DQ_ERR_INVALID, "null block table");
+    if (table_cap < ntiles)
+      return fail(DQ_ERR_INVALID, "block table capacity " + std::to_string(table_cap) + " below " +
+                                      std::to_string(ntiles) + " tiles");
+  } else {
+    shift = len ? (uint64_t)(p & 15u) : 0u;
+    obj0 = begin - shift;
+    ntiles = len ? (shift + len + kTileBytes - 1) / kTileBytes : 0u;
+  }
   if (ntiles >= 0xFFFF0000ull) return fail(DQ_ERR_INVALID, "range too large for one launch");
+  HIPCHK(hipSetDevice(c->device));
   const uint64_t words = kCtrlWords + ntiles;
   if (words > c->ws_words) {
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -432,19 +469,21 @@ int dq_records_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t
   HIPCHK(hipMemsetAsync(c->d_ws, 0, words * sizeof(unsigned long long), c->stream));
   if (ntiles) {
     QuoteArgs a;
-    a.base = (const uint8_t*)(p - shift);
+    a.base = (const uint8_t*)(p - (uintptr_t)shift);
     a.lo = shift;
     a.hi = shift + len;
-    a.obj0 = begin - shift;
+    a.obj0 = obj0;
     a.ntiles = ntiles;
     a.key_q = (quote * 0x01010101u) ^ kSel12;
     a.key_nl = 0x0A0A0A0Au ^ kSel12;
     a.carry = carry;
     a.out = d_out;
     a.cap = cap;
+    a.table = (unsigned long long*)d_table;
     a.ctrl = c->d_ws;
     const unsigned grid = (unsigned)(ntiles < (uint64_t)c->grid ? ntiles : (uint64_t)c->grid);
-    if (out_u64) hipLaunchKernelGGL(quote_kernel<1>, dim3(grid), dim3(kThreads), 0, c->stream, a);
+    if (form == 2) hipLaunchKernelGGL(quote_kernel<2>, dim3(grid), dim3(kThreads), 0, c->stream, a);
+    else if (form == 1) hipLaunchKernelGGL(quote_kernel<1>, dim3(grid), dim3(kThreads), 0, c->stream, a);
     else hipLaunchKernelGGL(quote_kernel<0>, dim3(grid), dim3(kThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
   }
@@ -454,6 +493,18 @@ int dq_records_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t
   c->count_only = cap == 0 && !d_out;
   c->in_flight = true;
   return DQ_OK;
+}
+
+int dq_records_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
+                     uint64_t end, uint32_t quote, uint32_t carry, void* d_out, int out_u64, uint64_t cap) {
+  if (out_u64 != 0 && out_u64 != 1) return fail(DQ_ERR_INVALID, "out_u64 must be 0 or 1");
+  return records_launch(c, d_buf, buf_len, buf_base, begin, end, quote, carry, d_out, out_u64, cap, nullptr, 0);
+}
+
+int dq_records_blocked_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
+                             uint64_t end, uint32_t quote, uint32_t carry, uint16_t* d_low, uint64_t cap,
+                             uint64_t* d_table, uint64_t table_cap) {
+  return records_launch(c, d_buf, buf_len, buf_base, begin, end, quote, carry, d_low, 2, cap, d_table, table_cap);
 }
 
 int dq_records_result(dq_ctx* c, uint64_t* n_out, uint64_t* n_quotes, uint64_t* n_newlines) {

@@ -23,7 +23,7 @@ from ..storage.errors import ClientError
 from ..version import __version__
 
 LINES_SUFFIX = ".lines"
-RECORDS_SUFFIX = ".records"        # quote-aware record ends (uint64 LE), beside the newline index
+RECORDS_SUFFIX = ".records"        # quote-aware record ends (uint64 LE, or u16b low words), beside the newline index
 _PRELOAD_BYTES = 256 << 20
 _BLOCK = 8192                      # entries per cached block for large indexes
 
@@ -224,13 +224,24 @@ def index_object(cloud_object, begin: int = 0, index_format: str = "auto", piece
 
 
 def store_record_index(cloud_object, offsets, quotechar: str) -> dict:
-    """PUT the quote-aware record ends (``scan.objects.record_index_object``) as uint64 LE at ``<key>.records``,
-    beside the newline index; returns the attributes that describe it."""
+    """PUT the quote-aware record ends (``scan.objects.record_index_object``) at ``<key>.records``, beside the
+    newline index; returns the attributes that describe it.
+
+    * a plain array: uint64 LE (no ``record_index_dtype`` attribute);
+    * ``scan.objects.BlockedOffsets`` (``record_index_dtype="u16b"``): uint16 LE low words, the 64 KiB block table
+      (uint64 LE) at ``<key>.records.blocks``, its first block in ``record_index_block0``."""
     key = cloud_object.meta_path.key + RECORDS_SUFFIX
-    cloud_object.storage.put_object(Body=np.ascontiguousarray(offsets, "<u8").tobytes(),
-                                    Bucket=cloud_object.meta_path.bucket, Key=key,
-                                    Metadata={"dataplug": __version__})
-    return {"record_index_key": key, "num_records": int(len(offsets)), "quotechar": quotechar}
+    st, bucket = cloud_object.storage, cloud_object.meta_path.bucket
+    meta = {"dataplug": __version__}
+    attrs = {"record_index_key": key, "num_records": int(len(offsets)), "quotechar": quotechar}
+    if hasattr(offsets, "table"):
+        bkey = key + ".blocks"
+        st.put_object(Body=np.ascontiguousarray(offsets.low, "<u2").data, Bucket=bucket, Key=key, Metadata=meta)
+        st.put_object(Body=np.ascontiguousarray(offsets.table, "<u8").data, Bucket=bucket, Key=bkey, Metadata=meta)
+        attrs.update(record_index_dtype="u16b", record_index_blocks_key=bkey, record_index_block0=int(offsets.j0))
+        return attrs
+    st.put_object(Body=np.ascontiguousarray(offsets, "<u8").tobytes(), Bucket=bucket, Key=key, Metadata=meta)
+    return attrs
 
 
 def records_of(cloud_object) -> "LineIndex":
@@ -241,8 +252,14 @@ def records_of(cloud_object) -> "LineIndex":
     if not key:
         raise KeyError(f"{cloud_object!r} has no record index: preprocess it with "
                        f"extra_args={{'quotechar': '\"'}}")
+    kw = {}
+    if getattr(attrs, "record_index_dtype", None) == "u16b":     # absent: uint64, as stored before the form existed
+        res = cloud_object.storage.get_object(Bucket=cloud_object.meta_path.bucket,
+                                              Key=getattr(attrs, "record_index_blocks_key"))
+        kw["blocks"] = np.frombuffer(res["Body"].read(), "<u8")
+        kw["block0"] = int(getattr(attrs, "record_index_block0"))
     return LineIndex(storage=cloud_object.storage, bucket=cloud_object.meta_path.bucket, key=key,
-                     count=getattr(attrs, "num_records", None))
+                     count=getattr(attrs, "num_records", None), **kw)
 
 
 def snap(records: "LineIndex", size: int, x: int) -> int:

@@ -12,6 +12,9 @@ Opt-in, beyond the reference: ``preprocess(extra_args={"quotechar": '"'})`` also
 (the ``'\\n'`` outside quoted fields, RFC 4180; built on the GPU by libdpquote.so) as uint64 at ``<key>.records``
 (attributes ``record_index_key``, ``num_records``, ``quotechar``), and ``partition_records_num_chunks`` /
 ``partition_records_chunk_size`` cut only at record ends, so a line break inside a quoted field never splits a row.
+``record_index_format="u16b"`` (default ``"u64"``) stores the same record ends in a quarter of the bytes: uint16 low
+words at ``<key>.records`` and the 64 KiB block table at ``<key>.records.blocks``, both written by the kernel
+(attributes ``record_index_dtype``, ``record_index_blocks_key``, ``record_index_block0``); the strategies read either.
 """
 from __future__ import annotations
 
@@ -31,8 +34,12 @@ logger = logging.getLogger(__name__)
 
 
 def preprocess_csv(cloud_object: "CloudObject", separator: str = ",", line_index: bool = True,
-                   index_format: str = "auto", quotechar: Optional[str] = None) -> PreprocessingMetadata:
+                   index_format: str = "auto", quotechar: Optional[str] = None,
+                   record_index_format: str = "u64") -> PreprocessingMetadata:
     import pandas as pd
+
+    if record_index_format not in ("u64", "u16b"):
+        raise ValueError(f"record_index_format must be 'u64' or 'u16b', not {record_index_format!r}")
 
     top = []
     with cloud_object.open("r") as f:
@@ -54,7 +61,9 @@ def preprocess_csv(cloud_object: "CloudObject", separator: str = ",", line_index
         if len(q) != 1 or q == b"\n":
             raise ValueError(f"quotechar must be one byte other than a newline, not {quotechar!r}")
         from ...scan import objects as so
-        attrs.update(store_record_index(cloud_object, so.record_index_object(cloud_object, quote=q[0]), quotechar))
+        kw = {} if record_index_format == "u64" else {"fmt": record_index_format}
+        attrs.update(store_record_index(cloud_object, so.record_index_object(cloud_object, quote=q[0], **kw),
+                                        quotechar))
     return PreprocessingMetadata(attributes=attrs)
 
 

@@ -32,7 +32,9 @@ SIGNATURES = [
     ("dq_ctx_create", _c.c_int, [_c.c_int, _p, _c.POINTER(_p)]),
     ("dq_ctx_destroy", _c.c_int, [_p]),
     ("dq_records_async", _c.c_int, [_p, _p, _u64, _u64, _u64, _u64, _c.c_uint32, _c.c_uint32, _p, _c.c_int, _u64]),
-    ("dq_records_result", _c.c_int, [_p, _u64p, _u64p, _u64p]),
+    ("dq_records_blocked_async", _c.c_int, [_p, _p, _u64, _u64, _u64, _u64, _c.c_uint32, _c.c_uint32, _p, _u64, _p,
+                                            _u64]),
+    ("dq_records_result",_c.c_int, [_p, _u64p, _u64p, _u64p]),
     ("dq_geometry", _c.c_int, [_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
 ]
 

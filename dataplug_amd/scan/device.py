@@ -464,6 +464,43 @@ class ScanContext:
                 continue
             return self.d2h(np.empty(n, dtype), out.ptr), nq, nn
 
+    def record_ends_blocked_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int,
+                                  carry: int, d_low: int, cap: int, d_table: int, table_cap: int) -> None:
+        """dq_records_blocked_async: uint16 low words at ``d_low``, the 64 KiB block table at ``d_table``; collected
+        by ``record_ends_result``.  The device address of ``begin`` must be congruent to ``begin`` mod 16."""
+        from . import _quote
+        q, h = self._quote_ctx()
+        _quote.check(q.dq_records_blocked_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote),
+                                                int(carry), ctypes.c_void_p(d_low or 0), int(cap),
+                                                ctypes.c_void_p(d_table or 0), int(table_cap)))
+
+    @staticmethod
+    def record_block_tiles(begin: int, end: int) -> int:
+        """Entries of the block table of object bytes [begin, end): the 64 KiB blocks that hold one of them."""
+        return ((end - 1) >> 16) - (begin >> 16) + 1 if end > begin else 0
+
+    def record_ends_blocked(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
+                            carry: int = 0, cap: Optional[int] = None):
+        """``record_ends`` in the blocked form u16b, written by the kernel: the low 16 bits of every record end's
+        object offset and ``table[j]`` = the record ends before object offset ``((begin >> 16) + j) << 16``
+        (``scan.objects.BlockedOffsets(low, table, begin >> 16)`` decodes them).
+
+        Returns (low uint16, table uint64, quote bytes seen, newlines seen)."""
+        if cap is None:
+            cap = (end - begin) // 16 + 1024
+        nt = self.record_block_tiles(begin, end)
+        while True:
+            out = self.workspace("out", cap * 2 + 16)
+            tab = self.workspace("record_blocks", nt * 8 + 16)
+            self.record_ends_blocked_async(d_buf, buf_len, buf_base, begin, end, quote, carry, out.ptr, cap,
+                                           tab.ptr, nt)
+            try:
+                n, nq, nn = self.record_ends_result()
+            except DPCapacityError as e:
+                cap = e.needed
+                continue
+            return self.d2h(np.empty(n, np.uint16), out.ptr), self.d2h(np.empty(nt, np.uint64), tab.ptr), nq, nn
+
     def find_delim(self, d_buf: int, buf_len: int, buf_base: int, start: int, delim: int = 10) -> int:
         """First object offset >= start holding ``delim`` in the buffer, or -1."""
         pos = ctypes.c_int64(-1)

@@ -618,17 +618,22 @@ def line_index_object(co, begin: int = 0, end: Optional[int] = None, delim: int 
 
 
 def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: int = 34,
-                        max_devices: Optional[int] = None, part_bytes: int = 8 << 30) -> np.ndarray:
-    """Sorted uint64 offsets of the record ends of object bytes [begin, end): the '\\n' bytes outside quoted fields
-    (an even number of ``quote`` bytes between ``begin`` and the newline; include/dpquote.h).
+                        max_devices: Optional[int] = None, part_bytes: int = 8 << 30, fmt: str = "u64"):
+    """Sorted offsets of the record ends of object bytes [begin, end): the '\\n' bytes outside quoted fields
+    (an even number of ``quote`` bytes between ``begin`` and the newline; include/dpquote.h).  ``fmt`` "u64": a
+    uint64 array; "u16b": a ``BlockedOffsets`` (uint16 low words + the 64 KiB block table, both written by the
+    kernel: a quarter of the bytes), the parts' tables merged by ``PieceMerge`` like a newline index's.
 
     The parts come from ``line_parts`` and run round-robin on the GPUs like a newline index.  A part does not know
     whether it starts inside a quoted field, so it runs two launches on its resident bytes: a count-only one that
     yields its number of quote bytes, and -- once the counts of every part before it are in, chained on the host
     into the part's incoming state -- the emitting one.  The second read is of HBM, not of the storage."""
+    if fmt not in ("u64", "u16b"):
+        raise ValueError(f"record index format must be 'u64' or 'u16b', not {fmt!r}")
     end = co.size if end is None else end
     if end <= begin:
-        return np.zeros(0, np.uint64)
+        return np.zeros(0, np.uint64) if fmt == "u64" else \
+            BlockedOffsets(np.zeros(0, np.uint16), np.zeros(1, np.uint64), begin >> 16)
     devs = devices(max_devices, co)
     bounds = line_parts(begin, end, len(devs), part_bytes)
     quotes = [0] * len(bounds)
@@ -651,8 +656,11 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
                     raise RuntimeError("record index: another part failed")
         carry = sum(quotes[:k]) & 1
         # the count under carry 0 bounds nothing under carry 1: size the output by the newlines only on a retry
-        out[k] = ctx.record_ends(dp, n, lo, lo, hi, quote=quote, carry=carry, u64=True,
-                                 cap=max(n_rec, 1) if carry == 0 else None)[0]
+        cap = max(n_rec, 1) if carry == 0 else None
+        if fmt == "u16b":                                # dp is congruent to lo mod 16: the blocked form's grid
+            out[k] = ctx.record_ends_blocked(dp, n, lo, lo, hi, quote=quote, carry=carry, cap=cap)[:2]
+        else:
+            out[k] = ctx.record_ends(dp, n, lo, lo, hi, quote=quote, carry=carry, u64=True, cap=cap)[0]
 
     by_dev = {}
     for k in range(len(bounds)):
@@ -677,7 +685,14 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
         if errors and errors[0] is not e:
             raise errors[0] from None
         raise
-    return out[0] if len(out) == 1 else np.concatenate(out)
+    if fmt == "u64":
+        return out[0] if len(out) == 1 else np.concatenate(out)
+    if len(out) == 1:                                    # one part: [begin, end) itself, its table as it is
+        return BlockedOffsets(out[0][0], out[0][1], begin >> 16)
+    merge = PieceMerge(begin, end, "u16b")
+    pieces = [merge.piece(lo, hi, o) for (lo, hi), o in zip(bounds, out)]
+    return BlockedOffsets(np.concatenate([p[0] for p in pieces]),
+                          np.concatenate([merge.head_table()] + [p[1] for p in pieces]), merge.J0)
 
 
 class PieceMerge:

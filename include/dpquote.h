@@ -59,6 +59,28 @@ int dq_ctx_destroy(dq_ctx* ctx);                           /* waits for the stre
 int dq_records_async(dq_ctx* ctx, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
                      uint64_t end, uint32_t quote, uint32_t carry, void* d_out, int out_u64, uint64_t cap);
 /*
+ * The same record ends in the blocked form u16b (the form scan.objects.BlockedOffsets and formats/_lines.LineIndex
+ * decode): a quarter of the bytes of the uint64 form, written by the kernel directly.  The additive entry point
+ * of ABI version 1; collected by dq_records_result like dq_records_async.
+ *   d_low receives, in ascending order, the low 16 bits of every record end's OBJECT offset (at most `cap`
+ *   entries, nothing at or beyond d_low[cap]; cap = 0 with d_low = NULL counts only).
+ *   d_table[j], j in 0 .. ntiles with ntiles = ((end - 1) >> 16) - (begin >> 16) + 1 (0 for an empty range),
+ *   receives the number of record ends of THIS launch that lie before object offset ((begin >> 16) + j) << 16:
+ *   d_table[0] = 0, and record end i lies in 64 KiB block (begin >> 16) + j for the largest j with
+ *   d_table[j] <= i, so its offset is (((begin >> 16) + j) << 16) | d_low[i].  Exactly ntiles entries are written
+ *   (whatever cap is) and nothing beyond them; table_cap is the room at d_table, in entries.
+ *   The kernel's 64 KiB tiles lie on the object's 64 KiB grid here, so a table entry is the output base a tile's
+ *   look-back resolves and a low word is the byte's position in its tile; no offset can overflow.
+ * Alignment rule: the 16-byte loads need the tile grid 16-byte aligned in device memory, so the device address
+ *   of object byte `begin`, d_buf + (begin - buf_base), must be congruent to `begin` mod 16 (the rule of
+ *   dp_delim_ranges out_modes 3 and 4).  Only 16-byte chunks that hold a byte of [begin, end) are read.
+ * DQ_ERR_INVALID: a non-empty range that breaks the alignment rule, table_cap < ntiles, d_table = NULL with a
+ *   non-empty range, d_low not 2-byte or d_table not 8-byte aligned, and every check of dq_records_async.
+ */
+int dq_records_blocked_async(dq_ctx* ctx, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base,
+                             uint64_t begin, uint64_t end, uint32_t quote, uint32_t carry, uint16_t* d_low,
+                             uint64_t cap, uint64_t* d_table, uint64_t table_cap);
+/*
  * Waits for the launch and returns its counts: *n_out record ends (the full count even beyond cap),
  * *n_quotes bytes == quote, *n_newlines bytes == '\n' (kept or not) in [begin, end); each may be NULL.
  *   DQ_ERR_CAPACITY: n_out > cap (the counts are still returned; the first cap entries are valid);

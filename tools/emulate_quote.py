@@ -1,4 +1,4 @@
-"""Lane-exact numpy model of quote_kernel<0|1> (dataplug_amd/csrc/dpquote.hip), for CPU validation.
+"""Lane-exact numpy model of quote_kernel<0|1|2> (dataplug_amd/csrc/dpquote.hip), for CPU validation.
 
 The kernel as written, not the definition (tests/_quote_model.py): the host arithmetic of dq_records_async, 64 KiB
 tiles of 4 waves x 16 rows x 64 lanes x 16-byte chunks, match4 as a v_perm_b32 byte table, mask16 as four signed-byte
@@ -14,6 +14,12 @@ deliberate defect (``MUTANTS``); tests/test_quote_model.py uses it to show that 
     prepare(...)  -> Prepared      host arithmetic, the launch's view of memory, phase A, the tile summaries
     finish(P,...) -> result        look-back under a schedule, phase B, the result words
     run(...)      = finish(prepare(...))
+
+The blocked form u16b (quote_kernel<2>, dq_records_blocked_async) is asked for by keyword: ``host_args(...,
+blocked=True)`` / ``prepare(..., blocked=True)`` lay the tiles on the object's 64 KiB grid (coordinate 0 = object
+offset begin & ~0xFFFF, lo up to 65535), and ``finish(..., fmt="u16b")`` / ``run(..., fmt="u16b")`` return
+``(low, table, n_out, n_quotes, n_newlines, err_bits)``: the uint16 low words and the block table (each tile's
+exclusive base).  ``BLOCKED_MUTANTS`` are the deliberate defects of that code; tests/test_quote_blocked_model.py.
 """
 from __future__ import annotations
 
@@ -47,14 +53,17 @@ MAX_TILES = 0xFFFF0000
 MUTANTS = ("then_swapped", "window_drops_f", "base_swapped", "ignore_carry", "no_run", "valid_hi_plus_one",
            "unsigned_dot", "agg_k1_shift16")
 
+# deliberate defects of the blocked form only (they change nothing in the uint32 / uint64 forms)
+BLOCKED_MUTANTS = ("table_inclusive", "low_from_shifted", "table_skip_tile0")
+
 M32 = 0xFFFFFFFF
 M64 = (1 << 64) - 1
 CANARY = 0xEEEEEEEEEEEEEEEE
 
 
 def _check_mutant(mutate):
-    if mutate is not None and mutate not in MUTANTS:
-        raise ValueError(f"mutate={mutate!r}: one of {MUTANTS}")
+    if mutate is not None and mutate not in MUTANTS and mutate not in BLOCKED_MUTANTS:
+        raise ValueError(f"mutate={mutate!r}: one of {MUTANTS + BLOCKED_MUTANTS}")
 
 
 # ------------------------------------------------------------------------------------------ instructions
@@ -282,8 +291,8 @@ def get_schedule(s):
 # ------------------------------------------------------------------------------------------ host side
 @dataclass(frozen=True)
 class Args:
-    """QuoteArgs as dq_records_async derives them; ``base_addr`` is the 16-byte aligned device address of
-    coordinate 0."""
+    """QuoteArgs as dq_records_async (dq_records_blocked_async with ``blocked``) derives them; ``base_addr`` is the
+    16-byte aligned device address of coordinate 0 (blocked: possibly below the buffer, never loaded from there)."""
     base_addr: int
     shift: int
     lo: int
@@ -294,18 +303,27 @@ class Args:
     key_nl: int
 
 
-def host_args(dev_addr: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34) -> Args:
+def host_args(dev_addr: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
+              blocked: bool = False) -> Args:
     if begin > end or begin < buf_base or end - buf_base > buf_len:
         raise ValueError("[begin, end) outside the buffer")
     if not 0 <= quote <= 255 or quote == 10:
         raise ValueError("quote must be a byte other than '\\n'")
     n = end - begin
     p = dev_addr + (begin - buf_base)
-    shift = (p & 15) if n else 0
-    ntiles = (shift + n + TILE_BYTES - 1) // TILE_BYTES if n else 0
+    if blocked:                                          # tiles on the object's 64 KiB grid
+        if n and (p ^ begin) & 15:
+            raise ValueError("blocked form: the device address of begin must be congruent to begin mod 16")
+        shift = (begin & 0xFFFF) if n else 0
+        obj0 = begin & ~0xFFFF
+        ntiles = ((end - 1) >> 16) - (begin >> 16) + 1 if n else 0
+    else:
+        shift = (p & 15) if n else 0
+        obj0 = (begin - shift) & M64
+        ntiles = (shift + n + TILE_BYTES - 1) // TILE_BYTES if n else 0
     if ntiles >= MAX_TILES:
         raise ValueError("range too large for one launch")
-    return Args(p - shift, shift, shift, shift + n, (begin - shift) & M64, ntiles,
+    return Args(p - shift, shift, shift, shift + n, obj0, ntiles,
                 ((quote * 0x01010101) & M32) ^ SEL12, 0x0A0A0A0A ^ SEL12)
 
 
@@ -321,6 +339,7 @@ class Prepared:
     tiles: List[Sum] = field(default_factory=list)
     n_quotes: int = 0
     n_newlines: int = 0
+    blocked: bool = False            # tiles on the object's 64 KiB grid (quote_kernel<2>)
 
 
 def launch_memory(buf: np.ndarray, dev_addr: int, a: Args, outside: bytes) -> np.ndarray:
@@ -330,30 +349,31 @@ def launch_memory(buf: np.ndarray, dev_addr: int, a: Args, outside: bytes) -> np
     mem = np.zeros(a.ntiles * TILE_BYTES, np.uint8)
     if a.ntiles == 0:
         return mem
-    top = (a.hi + 15) & ~15                              # lo < 16: the loaded chunks are coordinates [0, top)
-    pat = np.resize(np.frombuffer(outside, np.uint8), 16)
-    mem[:16] = pat                                       # [lo, hi) is inside the buffer: only the first and the
+    first, top = a.lo & ~15, (a.hi + 15) & ~15           # the loaded chunks are coordinates [first, top); first = 0
+    pat = np.resize(np.frombuffer(outside, np.uint8), 16)            # unless the form is blocked (lo up to 65535)
+    mem[first:first + 16] = pat                          # [lo, hi) is inside the buffer: only the first and the
     mem[top - 16:top] = pat                              # last chunk can reach beyond it
     c0 = dev_addr - a.base_addr                          # coordinate of buf[0]
-    x0, x1 = max(0, c0), min(top, c0 + len(buf))
+    x0, x1 = max(first, c0), min(top, c0 + len(buf))
     mem[x0:x1] = buf[x0 - c0:x1 - c0]
     return mem
 
 
 def prepare(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = None, end: Optional[int] = None,
-            quote: int = 34, mutate: Optional[str] = None, outside: bytes = b'"\n') -> Prepared:
+            quote: int = 34, mutate: Optional[str] = None, outside: bytes = b'"\n',
+            blocked: bool = False) -> Prepared:
     """Host arithmetic, phase A and the tile summaries of one launch over ``buf`` (the buffer's bytes, object bytes
     [buf_base, buf_base + len(buf))) placed at device address ``dev_addr``; only dev_addr mod 16 matters."""
     _check_mutant(mutate)
     buf = np.asarray(buf, np.uint8)
     begin = buf_base if begin is None else begin
     end = buf_base + len(buf) if end is None else end
-    a = host_args(dev_addr, len(buf), buf_base, begin, end, quote)
+    a = host_args(dev_addr, len(buf), buf_base, begin, end, quote, blocked)
     T = a.ntiles
     shape = (T, WAVES, ROWS, WAVE)
     if T == 0:
         z = np.zeros((0, WAVES), np.int64)
-        return Prepared(a, mutate, np.zeros(shape, np.int64), z, z, z, z)
+        return Prepared(a, mutate, np.zeros(shape, np.int64), z, z, z, z, blocked=blocked)
     mem = launch_memory(buf, dev_addr, a, outside)
     v = mem.view("<u4").reshape(shape + (4,))
     x = (np.arange(T * WAVES * ROWS * WAVE, dtype=np.int64) * 16).reshape(shape)     # x0 + row * kRowBytes
@@ -374,7 +394,7 @@ def prepare(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = No
     cnt = (popc(k0) | (popc(k1) << 16)).sum(2) & M32     # per lane over the rows
     cnt = cnt.sum(-1) & M32                              # wave_sum
     nq = popc(q).sum(2).sum(-1) & M32
-    P = Prepared(a, mutate, km, row_par.sum(-1) & 1, cnt & 0xFFFF, cnt >> 16, nq)
+    P = Prepared(a, mutate, km, row_par.sum(-1) & 1, cnt & 0xFFFF, cnt >> 16, nq, blocked=blocked)
     for t in range(T):
         s = IDENT
         for w in range(WAVES):
@@ -408,9 +428,10 @@ def resolve(P: Prepared, carry: int, schedule="sequential", mutate: Optional[str
     return state_in, base, n_out, stats
 
 
-def phase_b(P: Prepared, state_in, base, u64: bool, cap: int, out: np.ndarray) -> int:
+def phase_b(P: Prepared, state_in, base, u64: bool, cap: int, out: np.ndarray, u16b: bool = False,
+            mutate: Optional[str] = None) -> int:
     """The stores of phase B into ``out`` (entries at or beyond ``cap`` are never written); returns the overflow
-    flag and the number of stores that fell beyond ``out`` itself."""
+    flag and the number of stores that fell beyond ``out`` itself.  ``u16b``: the low words of the blocked form."""
     T = P.args.ntiles
     if T == 0:
         return 0, 0
@@ -437,7 +458,7 @@ def phase_b(P: Prepared, state_in, base, u64: bool, cap: int, out: np.ndarray) -
     total = np.where(single, tot1, tot5)                 # a row with any == 0 adds 0 either way
     row_base = wbase[:, :, None] + np.cumsum(total, axis=-1) - total
     i0 = (row_base[..., None] + ex).reshape(-1)          # the lane's first index
-    if cap == 0 and u64:
+    if cap == 0 and (u64 or u16b):
         return 0, 0                                      # nothing is stored and nothing can overflow
     bits = np.unpackbits(kept.astype("<u2").reshape(-1, 1).view(np.uint8), axis=1, bitorder="little")
     ch, bit = np.nonzero(bits)                           # chunk by chunk, lowest bit first: the while (kept) loop
@@ -445,20 +466,46 @@ def phase_b(P: Prepared, state_in, base, u64: bool, cap: int, out: np.ndarray) -
     first = np.cumsum(cc) - cc
     i = i0[ch] + (np.arange(len(ch)) - first[ch])
     o = np.uint64(P.args.obj0) + (ch.astype(np.uint64) * np.uint64(16) + bit.astype(np.uint64))   # mod 2^64
-    over = (o >> np.uint64(32)) != 0 if not u64 else np.zeros(len(o), bool)
+    over = (o >> np.uint64(32)) != 0 if not (u64 or u16b) else np.zeros(len(o), bool)
+    if u16b and mutate == "low_from_shifted":            # the coordinate of the other forms: from the 16-byte boundary
+        o = o - np.uint64(P.args.lo & ~15)               # at or below the first byte, not from the 64 KiB one
     w = ~over & (i < cap)
     stray = w & (i >= len(out))                          # beyond every possible count: only a mutant stores there
     w &= ~stray
-    out[i[w]] = o[w] if u64 else (o[w] & np.uint64(M32)).astype(np.uint32)
+    if u16b:
+        out[i[w]] = (o[w] & np.uint64(0xFFFF)).astype(np.uint16)
+    else:
+        out[i[w]] = o[w] if u64 else (o[w] & np.uint64(M32)).astype(np.uint32)
     return int(over.any()), int(stray.sum())
 
 
+def table_stores(P: Prepared, state_in, base, table: np.ndarray, mutate: Optional[str] = None) -> None:
+    """Wave 0's block table stores of the blocked form: table[tile] = the tile's exclusive base, after its
+    look-back, for every tile of the launch (0 for tile 0) -- whatever ``cap`` is."""
+    for t in range(P.args.ntiles):
+        if mutate == "table_skip_tile0" and t == 0:
+            continue
+        v = base[t]
+        if mutate == "table_inclusive":
+            v += P.tiles[t].k1 if state_in[t] else P.tiles[t].k0
+        table[t] = v
+
+
 def finish(P: Prepared, carry: int = 0, u64: bool = True, cap: Optional[int] = None, schedule="sequential",
-           mutate: Optional[str] = None, stats: Optional[dict] = None):
+           mutate: Optional[str] = None, stats: Optional[dict] = None, fmt: Optional[str] = None):
     """(offsets, n_out, n_quotes, n_newlines, err_bits) of the prepared launch.  ``cap=None`` is room for every
     newline; ``cap=0`` is the count-only launch (no capacity error).  ``offsets`` are the first min(n_out, cap)
     entries of the output array; ``stats`` receives the look-back statistics and the whole output array
-    ("out_raw", CANARY where nothing was stored)."""
+    ("out_raw", CANARY where nothing was stored).
+
+    ``fmt="u16b"`` (a launch prepared with ``blocked=True``): (low, table, n_out, n_quotes, n_newlines, err_bits),
+    the uint16 low words below ``cap`` and the ``ntiles`` block table entries; ``stats`` also receives the whole
+    table array ("table_raw", CANARY beyond the tiles)."""
+    if fmt not in (None, "u16b"):
+        raise ValueError(f"fmt={fmt!r}: None (the uint32 / uint64 forms, by u64=) or 'u16b'")
+    u16b = fmt == "u16b"
+    if u16b != P.blocked:
+        raise ValueError("fmt='u16b' goes with a launch prepared with blocked=True, and only with it")
     _check_mutant(mutate)
     if carry not in (0, 1):
         raise ValueError("carry must be 0 or 1")
@@ -466,9 +513,9 @@ def finish(P: Prepared, carry: int = 0, u64: bool = True, cap: Optional[int] = N
     state_in, base, n_out, st = resolve(P, carry, schedule, mutate)
     count_only = cap == 0
     cap = P.n_newlines if cap is None else cap
-    dt = np.uint64 if u64 else np.uint32
-    out = np.full(min(cap, P.n_newlines) + 64, CANARY if u64 else CANARY & M32, dt)
-    overflow, stray = phase_b(P, state_in, base, u64, cap, out)
+    dt = np.uint16 if u16b else (np.uint64 if u64 else np.uint32)
+    out = np.full(min(cap, P.n_newlines) + 64, CANARY & (2 ** (8 * np.dtype(dt).itemsize) - 1), dt)
+    overflow, stray = phase_b(P, state_in, base, u64, cap, out, u16b, mutate)
     err = ERR_OVERFLOW if overflow else 0
     if n_out > cap and not count_only:
         err |= ERR_CAPACITY
@@ -476,13 +523,23 @@ def finish(P: Prepared, carry: int = 0, u64: bool = True, cap: Optional[int] = N
         err |= ERR_STRAY
     if stats is not None:
         stats.update(st, out_raw=out, state_in=state_in, base=base)
+    if u16b:
+        table = np.full(P.args.ntiles + 8, CANARY, np.uint64)
+        table_stores(P, state_in, base, table, mutate)
+        if stats is not None:
+            stats.update(table_raw=table)
+        return out[:min(n_out, cap)], table[:P.args.ntiles], n_out, P.n_quotes, P.n_newlines, err
     return out[:min(n_out, cap)], n_out, P.n_quotes, P.n_newlines, err
 
 
 def run(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = None, end: Optional[int] = None,
         quote: int = 34, carry: int = 0, u64: bool = True, cap: Optional[int] = None, schedule="sequential",
-        mutate: Optional[str] = None, outside: bytes = b'"\n', stats: Optional[dict] = None):
+        mutate: Optional[str] = None, outside: bytes = b'"\n', stats: Optional[dict] = None,
+        fmt: Optional[str] = None):
     """One launch, as ScanContext.record_ends_async + record_ends_result see it:
-    (offsets, n_out, n_quotes, n_newlines, err_bits)."""
-    return finish(prepare(buf, dev_addr, buf_base, begin, end, quote, mutate, outside), carry, u64, cap, schedule,
-                  mutate, stats)
+    (offsets, n_out, n_quotes, n_newlines, err_bits); with ``fmt="u16b"`` as record_ends_blocked_async does:
+    (low, table, n_out, n_quotes, n_newlines, err_bits)."""
+    if fmt not in (None, "u16b"):
+        raise ValueError(f"fmt={fmt!r}: None (the uint32 / uint64 forms, by u64=) or 'u16b'")
+    return finish(prepare(buf, dev_addr, buf_base, begin, end, quote, mutate, outside, fmt == "u16b"), carry, u64,
+                  cap, schedule, mutate, stats, fmt)

@@ -7,10 +7,12 @@ the asked size (whole blocks, so the expected record ends are the block's, shift
 process, alternating launch by launch after a warm-up of each:
 * ``dq_records_async`` (uint64 output), HIP events on the context stream around the whole call: the per-launch
   zeroing of the descriptors, the kernel and the 64-byte result copy;
+* ``dq_records_blocked_async`` (u16b: uint16 low words + the 64 KiB block table), timed the same way;
 * ``dp_stream_read``, the read-only calibration kernel, and ``dp_delim_index`` (uint64), the newline index, each timed
   by the library's own HIP events around its kernels (dp_timing_enable).
-Prints one JSON line: the three times and GiB/s (input bytes over time), the ratio of the record index's rate to each
-of the other two, and whether the last record-index output equals the numpy model.
+Prints one JSON line: the times and GiB/s (input bytes over time), the ratio of each record-index form's rate to the
+read-only kernel's (and of the uint64 form's to the newline index's), the u16b form's time over the uint64 form's, and
+whether the last output of each form, the u16b one decoded, equals the numpy model.
 """
 from __future__ import annotations
 
@@ -26,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dataplug_amd import synth  # noqa: E402
 from dataplug_amd.scan import get_context  # noqa: E402
+from dataplug_amd.scan.objects import BlockedOffsets  # noqa: E402
 
 GiB = float(1 << 30)
 
@@ -84,12 +87,21 @@ def main():
     cap = len(exp) + 1024
     nl_cap = copies * int(np.count_nonzero(block == 10)) + 1024
     out = ctx.workspace("quote_rate_out", 8 * max(cap, nl_cap))
+    nt = ctx.record_block_tiles(0, n)
+    low = ctx.workspace("quote_rate_low", 2 * cap)
+    tab = ctx.workspace("quote_rate_blocks", 8 * nt)
     ev = Events(ctx.stream)
     n16 = n // 16 * 16
 
     def quote():
         ev.start()
         ctx.record_ends_async(d.ptr, n, 0, 0, n, 34, 0, out.ptr, True, cap)
+        ms = ev.stop_ms()
+        return ms, ctx.record_ends_result()
+
+    def quote16():
+        ev.start()
+        ctx.record_ends_blocked_async(d.ptr, n, 0, 0, n, 34, 0, low.ptr, cap, tab.ptr, nt)
         ms = ev.stop_ms()
         return ms, ctx.record_ends_result()
 
@@ -111,11 +123,13 @@ def main():
 
     ctx.timing(True)
     for _ in range(2):                                              # warm-up of every kernel at this size
-        quote(), read(), delim()
-    tq, tr, td = [], [], []
+        quote(), quote16(), read(), delim()
+    tq, tb, tr, td = [], [], [], []
     for _ in range(args.reps):
         tr.append(read())
         td.append(delim())
+        ms, res16 = quote16()
+        tb.append(ms)
         ms, (n_out, n_quotes, n_newlines) = quote()                 # last: its output is the one verified
         tq.append(ms)
     ctx.timing(False)
@@ -123,20 +137,28 @@ def main():
     ok = bool(n_out == len(exp) and np.array_equal(got, exp) and n_quotes == copies * int(np.count_nonzero(block == 34))
               and n_newlines == copies * int(np.count_nonzero(block == 10)))
 
+    got16 = BlockedOffsets(ctx.d2h(np.empty(res16[0], np.uint16), low.ptr), ctx.d2h(np.empty(nt, np.uint64), tab.ptr),
+                           0).to_u64()
+    ok16 = bool(res16 == (n_out, n_quotes, n_newlines) and np.array_equal(got16, exp))
+
     def rate(ts, nbytes):
         return round(nbytes / (float(np.median(ts)) / 1e3) / GiB, 1)
 
-    rq, rr, rd = rate(tq, n), rate(tr, n16), rate(td, n)
+    rq, rb, rr, rd = rate(tq, n), rate(tb, n), rate(tr, n16), rate(td, n)
     print(json.dumps({
         "bytes": n, "records": int(n_out), "newlines": int(n_newlines), "quotes": int(n_quotes), "reps": args.reps,
         "tile_bytes_grid": list(ctx.quote_geometry()),
         "record_index_ms": [round(float(np.median(tq)), 3), round(min(tq), 3), round(max(tq), 3)],
+        "record_index_u16b_ms": [round(float(np.median(tb)), 3), round(min(tb), 3), round(max(tb), 3)],
         "stream_read_ms": [round(float(np.median(tr)), 3), round(min(tr), 3), round(max(tr), 3)],
         "newline_index_ms": [round(float(np.median(td)), 3), round(min(td), 3), round(max(td), 3)],
         "record_index_GiB_per_s": rq, "stream_read_GiB_per_s": rr, "newline_index_u64_GiB_per_s": rd,
         "ratio_to_stream_read": round(rq / rr, 3), "ratio_to_newline_index": round(rq / rd, 3),
-        "newline_index_form": ctx.last_delim_form(), "verified": ok}), flush=True)
-    return 0 if ok else 1
+        "record_index_u16b_GiB_per_s": rb, "u16b_ratio_to_stream_read": round(rb / rr, 3),
+        "u16b_ms_over_u64_ms": round(float(np.median(tb)) / float(np.median(tq)), 3),
+        "index_bytes": {"u64": 8 * int(n_out), "u16b": 2 * int(n_out) + 8 * nt},
+        "newline_index_form": ctx.last_delim_form(), "verified": ok, "verified_u16b": ok16}), flush=True)
+    return 0 if ok and ok16 else 1
 
 
 if __name__ == "__main__":
