@@ -18,6 +18,15 @@
 // at or below the range's first byte), and the blocked form u16b (dq_records_blocked_async): tiles lie on the object's
 // 64 KiB grid, so a record end's uint16 low word is its position in the tile and the block table entry of a tile is
 // the exclusive base its look-back resolves anyway.
+//
+// Escape-aware variant (second template parameter, dq_records_esc_async / dq_records_esc_blocked_async): a byte that
+// follows an unescaped escape byte is literal.  The "this byte is escaped" bit is resolved before the masks are
+// summarized -- escaped quotes leave the quote mask, under scope "all" escaped newlines leave the newline mask -- so
+// the summaries, the descriptors, the look-back and phase B are those of the plain kernel.  Inside a chunk the escaped
+// bytes come from one add-carry over the escape mask; across the lanes of a row from two ballots (all-escape chunks
+// pass the incoming bit on, every other chunk sets it to the parity of its trailing escape run); across rows from
+// scalar work on those ballots; and at its 16 KiB start a wave reads the chunks just before it, walking further back
+// only while they hold nothing but escape bytes (at most DQ_ESCAPE_RUN_MAX bytes, then DQ_ERR_ESCAPE_RUN: no wait).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,6 +52,12 @@ static_assert(kWaveBytes <= 0xFFFF, "wave counts are packed in 16 bits");
 constexpr uint32_t kSel12 = 0x0C0C0C0Cu;           // v_perm selector that yields 0x00
 constexpr uint32_t kErrTimeout = 1u;
 constexpr uint32_t kErrOverflow = 2u;
+constexpr uint32_t kErrEscapeRun = 4u;
+constexpr uint32_t kOddBits = 0xAAAAAAAAu;
+// a wave's walk back over all-escape chunks: whole windows of 64 chunks, then the one chunk beyond the bound
+constexpr uint32_t kEscWindows = (uint32_t)(DQ_ESCAPE_RUN_MAX / (64 * 16));
+static_assert(DQ_ESCAPE_RUN_MAX % (64 * 16) == 0 && DQ_ESCAPE_RUN_MAX >= (1 << 16) + 16,
+              "the bound is whole windows and at least a tile plus a chunk");
 
 // Descriptor word (one 64-bit atomic store, zero = not published):
 //   AGG     bits 0..23 kept0, 24..47 kept1, 48 parity  -- the tile as a function of its incoming state
@@ -53,6 +68,7 @@ constexpr uint64_t kCountMask = 0xFFFFFFFFFFFFull;
 
 // control words at the head of the workspace (uint64 each), descriptors follow at kCtrlWords
 constexpr int kCtrlTicket = 0, kCtrlErr = 1, kCtrlOut = 2, kCtrlQuotes = 3, kCtrlNewlines = 4;
+constexpr int kCtrlToggles = 5;                      // escape-aware launches: the quotes that are not escaped
 constexpr int kCtrlWords = 8;
 
 constexpr uint64_t kWaitTicks = 100000000ull * 20;   // 20 s of the 100 MHz realtime counter
@@ -79,6 +95,10 @@ struct QuoteArgs {
   uint64_t cap;
   unsigned long long* table;   // blocked form: ntiles entries, the record ends of the launch before each tile
   unsigned long long* ctrl;    // kCtrlWords control words, then ntiles descriptors
+  // escape-aware launches only
+  uint32_t key_e;              // match4 key of the escape byte
+  uint32_t esc_carry;          // 1: the byte at lo is escaped
+  uint32_t esc_nl;             // 0xFFFF: an escaped '\n' is no record end (scope "all"); 0: scope "quoted"
 };
 
 // 0x00 in every byte of w that equals the key's pattern byte, 0xFF in every other byte (exact).
@@ -102,6 +122,29 @@ __device__ __forceinline__ uint32_t valid16(uint64_t x, uint64_t lo, uint64_t hi
   const uint32_t a = lo > x ? (uint32_t)(lo - x) : 0u;              // < 16
   const uint32_t b = hi - x < 16u ? (uint32_t)(hi - x) : 16u;       // 1..16
   return (0xFFFFu >> (16u - b)) & (0xFFFFu << a);
+}
+// Escape bytes e of a chunk (16 bits) and the bit `in` of the byte that is escaped on entry (at most one bit, zero
+// for none): the add-carry over runs of escape bytes.  With c = esc_code(e, in), the escaped bytes are
+// (c ^ (e | in)) & 0xFFFF and bit 15 of c & e says that the byte after the chunk is escaped.
+__device__ __forceinline__ uint32_t esc_code(uint32_t e, uint32_t in) {
+  const uint32_t pot = e & ~in;                    // escape bytes that are not escaped by the carry
+  return (((pot << 1) | kOddBits) - pot) ^ kOddBits;
+}
+// A chunk as the row chain sees it: a = all 16 bytes are escape bytes (16 is even: the incoming bit passes through),
+// t = the bit it hands on otherwise (the parity of its trailing escape run).  The chunk that holds the byte at lo
+// starts the chain: its incoming bit is the launch's esc_carry, at that byte, and it never passes anything through.
+struct EscChunk {
+  uint32_t e, in0, a, t;
+  bool first;
+};
+__device__ __forceinline__ EscChunk esc_chunk(const uint4& v, uint32_t ok, uint64_t x, const QuoteArgs& A) {
+  EscChunk c;
+  c.e = mask16(v, A.key_e) & ok;
+  c.first = x <= A.lo && A.lo < x + 16u;
+  c.in0 = c.first ? A.esc_carry << (uint32_t)(A.lo - x) : 0u;
+  c.a = (c.e == 0xFFFFu && !c.first) ? 1u : 0u;
+  c.t = ((esc_code(c.e, c.in0) & c.e) >> 15) & 1u;
+  return c;
 }
 __device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -193,8 +236,41 @@ __device__ __forceinline__ bool look_back(const QuoteArgs& A, uint64_t tile, int
   }
 }
 
+// Is the byte at coordinate xw, the wave's first, escaped?  Wave-uniform.  Lane l reads the (l + 1)-th chunk before
+// xw -- like every load of the kernel only if the chunk holds a byte of [lo, hi) -- and the nearest chunk that is not
+// all escape bytes decides; chunks below lo are not read and decide 0, but the chunk of lo is nearer and always
+// decides.  After kEscWindows windows of nothing but escape bytes one more chunk is looked at: a run that covers it
+// too is beyond DQ_ESCAPE_RUN_MAX and ends the launch with kErrEscapeRun (no wait: descriptors are published as usual).
+__device__ __forceinline__ uint32_t wave_esc_in(const QuoteArgs& A, uint64_t xw, int lane) {
+  if (xw <= A.lo || xw >= A.hi) return 0u;         // the chain starts in this wave, or the wave holds no byte
+  for (uint32_t it = 0;; ++it) {
+    const uint64_t back = ((uint64_t)it * kWave + (uint64_t)lane + 1u) * 16u;
+    uint32_t ca = 0u, ct = 0u;
+    if (back <= xw) {
+      const uint64_t x = xw - back;                // x < xw < hi
+      if (x < A.hi && x + 16u > A.lo) {            // the chunk holds a byte of [lo, hi): inside the buffer's pages
+        const uint4 v = *reinterpret_cast<const uint4*>(A.base + x);
+        const EscChunk c = esc_chunk(v, valid16(x, A.lo, A.hi), x, A);
+        ca = c.a;
+        ct = c.t;
+      }
+    }
+    const uint64_t ba = __ballot(ca != 0u), bt = __ballot(ct != 0u);
+    if (it == kEscWindows) {
+      if (ba & 1ull) {
+        if (lane == 0) atomicOr(reinterpret_cast<unsigned int*>(A.ctrl + kCtrlErr), kErrEscapeRun);
+        return 0u;
+      }
+      return (uint32_t)bt & 1u;
+    }
+    const uint64_t stop = ~ba;
+    if (stop) return (uint32_t)(bt >> __builtin_ctzll(stop)) & 1u;
+  }
+}
+
 // OUT64: 0 uint32 offsets, 1 uint64 offsets, 2 uint16 low words + the 64 KiB block table (tiles on the object's grid)
-template <int OUT64>
+// ESC: 1 honours the escape byte (key_e, esc_carry, esc_nl)
+template <int OUT64, int ESC>
 __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
   __shared__ Shared S;
   using OutT = typename std::conditional<OUT64 == 1, uint64_t,
@@ -215,7 +291,9 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
     // ---- phase A: masks, in-wave parity, the newlines kept under either incoming state
     uint32_t km[kRows];                            // bits 0..15 kept if the wave is entered outside, 16..31 inside
     uint32_t run = 0;                              // parity of the wave's rows so far (wave-uniform)
-    uint32_t cnt = 0, nq = 0;                      // per lane: kept0 | kept1 << 16; quotes
+    uint32_t cnt = 0, nq = 0;                      // per lane: kept0 | kept1 << 16; quotes (ESC: | unescaped << 16)
+    uint32_t erow = 0;                             // ESC: is the row's first byte escaped (wave-uniform)
+    if (ESC) erow = wave_esc_in(A, x0 - (uint64_t)lane * 16u, lane);
 #pragma unroll
     for (int h = 0; h < kRows; h += kHalf) {
       uint4 v[kHalf];
@@ -233,8 +311,21 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
       }
 #pragma unroll
       for (int r = 0; r < kHalf; ++r) {
-        const uint32_t q = mask16(v[r], A.key_q) & ok[r];
-        const uint32_t n = mask16(v[r], A.key_nl) & ok[r];
+        uint32_t q = mask16(v[r], A.key_q) & ok[r];
+        uint32_t n = mask16(v[r], A.key_nl) & ok[r];
+        if (ESC) {
+          const EscChunk c = esc_chunk(v[r], ok[r], x0 + (uint64_t)(h + r) * kRowBytes, A);
+          const uint64_t ba = __ballot(c.a != 0u), bt = __ballot(c.t != 0u);
+          // the bit of the nearest lane below that is not all escape bytes, or the row's
+          const uint64_t stop = ~ba & ((1ull << lane) - 1ull);
+          uint32_t in = stop ? (uint32_t)(bt >> (63 - __builtin_clzll(stop))) & 1u : erow;
+          if (c.first) in = c.in0;                 // the chunk of lo: esc_carry, at that byte
+          const uint32_t escaped = (esc_code(c.e, in) ^ (c.e | in)) & 0xFFFFu;
+          nq += (uint32_t)__popc(q) << 16;         // the quote bytes; below, the low half counts the unescaped ones
+          q &= ~escaped;
+          n &= ~(escaped & A.esc_nl);
+          if (~ba) erow = (uint32_t)(bt >> (63 - __builtin_clzll(~ba))) & 1u;   // the next row's, scalar
+        }
         uint32_t px = q;                           // bit i: parity of the chunk's quotes in bytes 0..i
         px ^= px << 1;
         px ^= px << 2;
@@ -263,11 +354,14 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
     // ---- the tile's summary, its look-back, its descriptors (wave 0)
     if (wave == 0) {
       Sum t{0u, 0ull, 0ull};
-      uint32_t tq = 0, tn = 0;
+      uint32_t tq = 0, tn = 0, tt = 0;
 #pragma unroll
       for (int w = 0; w < kWaves; ++w) {
         t = then(t, Sum{S.wpar[w], S.wk0[w], S.wk1[w]});
-        tq += S.wq[w];
+        if (ESC) {
+          tq += S.wq[w] >> 16;
+          tt += S.wq[w] & 0xFFFFu;
+        } else tq += S.wq[w];
         tn += S.wk0[w] + S.wk1[w];
       }
       uint32_t state_in = A.carry;
@@ -291,6 +385,7 @@ __global__ void __launch_bounds__(kThreads) quote_kernel(QuoteArgs A) {
         if (OUT64 == 2) A.table[tile] = base;      // the record ends before the tile: its entry of the block table
         if (tq) atomicAdd(A.ctrl + kCtrlQuotes, (unsigned long long)tq);
         if (tn) atomicAdd(A.ctrl + kCtrlNewlines, (unsigned long long)tn);
+        if (ESC && tt) atomicAdd(A.ctrl + kCtrlToggles, (unsigned long long)tt);
         if (tile + 1 == A.ntiles) A.ctrl[kCtrlOut] = incl;
       }
     }
@@ -359,12 +454,14 @@ int fail(int code, const std::string& msg) {
 struct dq_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  int grid = 0;                       // workgroups of the persistent grid
+  int grid = 0;                       // workgroups of the persistent grid (the plain instantiations)
+  int grid_esc[3] = {0, 0, 0};        // ... of the escape-aware instantiation of each output form
   unsigned long long* d_ws = nullptr; // control words + descriptors (grow-only)
   uint64_t ws_words = 0;
   unsigned long long* h_res = nullptr;  // pinned copy of the control words
   bool in_flight = false;
   bool count_only = false;            // cap = 0 with d_out = NULL: no capacity error
+  bool escaped = false;               // the launch in flight is an escape-aware one
   uint64_t cap = 0;
 };
 
@@ -384,20 +481,30 @@ int dq_ctx_create(int device, void* stream, dq_ctx** out) {
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
   int occ = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, quote_kernel<0>, kThreads, 0));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, quote_kernel<0, 0>, kThreads, 0));
   int occ1 = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, quote_kernel<1>, kThreads, 0));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ1, quote_kernel<1, 0>, kThreads, 0));
   if (occ1 < occ) occ = occ1;
   int occ2 = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, quote_kernel<2>, kThreads, 0));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ2, quote_kernel<2, 0>, kThreads, 0));
   if (occ2 < occ) occ = occ2;
   if (occ < 1) return fail(DQ_ERR_HIP, "quote_kernel: no resident workgroup per CU");
   if (occ > kMaxBlocksPerCU) occ = kMaxBlocksPerCU;
+  // the escape-aware instantiations size their own grids: a lower occupancy there does not shrink the grid above
+  int occ_esc[3] = {0, 0, 0};
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_esc[0], quote_kernel<0, 1>, kThreads, 0));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_esc[1], quote_kernel<1, 1>, kThreads, 0));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_esc[2], quote_kernel<2, 1>, kThreads, 0));
+  for (int f = 0; f < 3; ++f) {
+    if (occ_esc[f] < 1) return fail(DQ_ERR_HIP, "quote_kernel (escape): no resident workgroup per CU");
+    if (occ_esc[f] > kMaxBlocksPerCU) occ_esc[f] = kMaxBlocksPerCU;
+  }
   dq_ctx* c = new dq_ctx();
   c->device = device;
   c->stream = (hipStream_t)stream;
   // the grid need not be resident (tiles are claimed by running workgroups); this size merely fills the chip
   c->grid = prop.multiProcessorCount * occ;
+  for (int f = 0; f < 3; ++f) c->grid_esc[f] = prop.multiProcessorCount * occ_esc[f];
   hipError_t e = hipHostMalloc((void**)&c->h_res, kCtrlWords * sizeof(unsigned long long), hipHostMallocDefault);
   if (e != hipSuccess) {
     delete c;
@@ -417,11 +524,17 @@ int dq_ctx_destroy(dq_ctx* c) {
   return DQ_OK;
 }
 
-// The launch behind both entry points.  form: 0 uint32, 1 uint64 (coordinate 0 = the 16-byte boundary at or below
+// The escape arguments of a launch; `on` = false is the plain kernel.
+struct EscSpec {
+  bool on;
+  uint32_t escape, esc_carry, flags;
+};
+
+// The launch behind every entry point.  form: 0 uint32, 1 uint64 (coordinate 0 = the 16-byte boundary at or below
 // the device address of `begin`), 2 blocked (coordinate 0 = object offset begin & ~0xFFFF, d_table required).
 static int records_launch(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
                           uint64_t end, uint32_t quote, uint32_t carry, void* d_out, int form, uint64_t cap,
-                          uint64_t* d_table, uint64_t table_cap) {
+                          uint64_t* d_table, uint64_t table_cap, const EscSpec& esc = EscSpec{false, 0u, 0u, 0u}) {
   if (!c) return fail(DQ_ERR_INVALID, "null ctx");
   if (c->in_flight) return fail(DQ_ERR_INVALID, "a launch is in flight: collect it with dq_records_result");
   if (begin > end || begin < buf_base || end - buf_base > buf_len)
@@ -429,6 +542,12 @@ static int records_launch(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uin
   if (end > begin && !d_buf) return fail(DQ_ERR_INVALID, "null buffer");
   if (quote > 255u || quote == 10u) return fail(DQ_ERR_INVALID, "quote must be a byte other than '\\n'");
   if (carry > 1u) return fail(DQ_ERR_INVALID, "carry must be 0 or 1");
+  if (esc.on) {
+    if (esc.escape > 255u || esc.escape == 10u || esc.escape == quote)
+      return fail(DQ_ERR_INVALID, "escape must be a byte other than the quote and '\\n'");
+    if (esc.esc_carry > 1u) return fail(DQ_ERR_INVALID, "esc_carry must be 0 or 1");
+    if (esc.flags & ~(uint32_t)DQ_ESC_SCOPE_QUOTED) return fail(DQ_ERR_INVALID, "unknown escape flags");
+  }
   if (cap && !d_out) return fail(DQ_ERR_INVALID, "null output with cap > 0");
   if (form < 0 || form > 2) return fail(DQ_ERR_INVALID, "out_u64 must be 0 or 1");
   if (cap && ((uintptr_t)d_out & (form == 1 ? 7u : form == 2 ? 1u : 3u)))
@@ -481,10 +600,18 @@ static int records_launch(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uin
     a.cap = cap;
     a.table = (unsigned long long*)d_table;
     a.ctrl = c->d_ws;
-    const unsigned grid = (unsigned)(ntiles < (uint64_t)c->grid ? ntiles : (uint64_t)c->grid);
-    if (form == 2) hipLaunchKernelGGL(quote_kernel<2>, dim3(grid), dim3(kThreads), 0, c->stream, a);
-    else if (form == 1) hipLaunchKernelGGL(quote_kernel<1>, dim3(grid), dim3(kThreads), 0, c->stream, a);
-    else hipLaunchKernelGGL(quote_kernel<0>, dim3(grid), dim3(kThreads), 0, c->stream, a);
+    a.key_e = esc.on ? (esc.escape * 0x01010101u) ^ kSel12 : 0u;
+    a.esc_carry = esc.on ? esc.esc_carry : 0u;
+    a.esc_nl = esc.on && !(esc.flags & DQ_ESC_SCOPE_QUOTED) ? 0xFFFFu : 0u;
+    const uint64_t full = (uint64_t)(esc.on ? c->grid_esc[form] : c->grid);
+    const unsigned grid = (unsigned)(ntiles < full ? ntiles : full);
+    if (esc.on) {
+      if (form == 2) hipLaunchKernelGGL((quote_kernel<2, 1>), dim3(grid), dim3(kThreads), 0, c->stream, a);
+      else if (form == 1) hipLaunchKernelGGL((quote_kernel<1, 1>), dim3(grid), dim3(kThreads), 0, c->stream, a);
+      else hipLaunchKernelGGL((quote_kernel<0, 1>), dim3(grid), dim3(kThreads), 0, c->stream, a);
+    } else if (form == 2) hipLaunchKernelGGL((quote_kernel<2, 0>), dim3(grid), dim3(kThreads), 0, c->stream, a);
+    else if (form == 1) hipLaunchKernelGGL((quote_kernel<1, 0>), dim3(grid), dim3(kThreads), 0, c->stream, a);
+    else hipLaunchKernelGGL((quote_kernel<0, 0>), dim3(grid), dim3(kThreads), 0, c->stream, a);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipMemcpyAsync(c->h_res, c->d_ws, kCtrlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost,
@@ -492,6 +619,7 @@ static int records_launch(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uin
   c->cap = cap;
   c->count_only = cap == 0 && !d_out;
   c->in_flight = true;
+  c->escaped = esc.on;
   return DQ_OK;
 }
 
@@ -507,6 +635,34 @@ int dq_records_blocked_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, 
   return records_launch(c, d_buf, buf_len, buf_base, begin, end, quote, carry, d_low, 2, cap, d_table, table_cap);
 }
 
+int dq_records_esc_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
+                         uint64_t end, uint32_t quote, uint32_t carry, uint32_t escape, uint32_t esc_carry,
+                         uint32_t flags, void* d_out, int out_u64, uint64_t cap) {
+  if (out_u64 != 0 && out_u64 != 1) return fail(DQ_ERR_INVALID, "out_u64 must be 0 or 1");
+  return records_launch(c, d_buf, buf_len, buf_base, begin, end, quote, carry, d_out, out_u64, cap, nullptr, 0,
+                        EscSpec{true, escape, esc_carry, flags});
+}
+
+int dq_records_esc_blocked_async(dq_ctx* c, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base,
+                                 uint64_t begin, uint64_t end, uint32_t quote, uint32_t carry, uint32_t escape,
+                                 uint32_t esc_carry, uint32_t flags, uint16_t* d_low, uint64_t cap,
+                                 uint64_t* d_table, uint64_t table_cap) {
+  return records_launch(c, d_buf, buf_len, buf_base, begin, end, quote, carry, d_low, 2, cap, d_table, table_cap,
+                        EscSpec{true, escape, esc_carry, flags});
+}
+
+int dq_records_esc_result(dq_ctx* c, uint64_t* n_out, uint64_t* n_quotes, uint64_t* n_newlines,
+                          uint64_t* n_toggles) {
+  // (a plain launch toggles at every quote byte)
+  if (c && c->in_flight && n_toggles) {
+    const bool escaped = c->escaped;
+    const int rc = dq_records_result(c, n_out, n_quotes, n_newlines);
+    *n_toggles = c->h_res[escaped ? kCtrlToggles : kCtrlQuotes];
+    return rc;
+  }
+  return dq_records_result(c, n_out, n_quotes, n_newlines);
+}
+
 int dq_records_result(dq_ctx* c, uint64_t* n_out, uint64_t* n_quotes, uint64_t* n_newlines) {
   if (!c) return fail(DQ_ERR_INVALID, "null ctx");
   if (!c->in_flight) return fail(DQ_ERR_INVALID, "no launch in flight");
@@ -518,6 +674,8 @@ int dq_records_result(dq_ctx* c, uint64_t* n_out, uint64_t* n_quotes, uint64_t* 
   if (n_quotes) *n_quotes = c->h_res[kCtrlQuotes];
   if (n_newlines) *n_newlines = c->h_res[kCtrlNewlines];
   if (err & kErrTimeout) return fail(DQ_ERR_TIMEOUT, "a look-back wait exceeded its bound: results invalid");
+  if (err & kErrEscapeRun)
+    return fail(DQ_ERR_ESCAPE_RUN, "a run of escape bytes longer than DQ_ESCAPE_RUN_MAX: results invalid");
   if (err & kErrOverflow) return fail(DQ_ERR_OVERFLOW, "a record end lies at an offset >= 2^32 (uint32 output)");
   if (c->h_res[kCtrlOut] > c->cap && !c->count_only)
     return fail(DQ_ERR_CAPACITY, "output capacity " + std::to_string(c->cap) + " below " +

@@ -223,7 +223,8 @@ def index_object(cloud_object, begin: int = 0, index_format: str = "auto", piece
     return store_line_index(cloud_object, so.line_index_object(cloud_object, begin=begin, end=end, fmt=fmt))
 
 
-def store_record_index(cloud_object, offsets, quotechar: str) -> dict:
+def store_record_index(cloud_object, offsets, quotechar: str, escapechar: Optional[str] = None,
+                       escape_scope: Optional[str] = None) -> dict:
     """PUT the quote-aware record ends (``scan.objects.record_index_object``) at ``<key>.records``, beside the
     newline index; returns the attributes that describe it.
 
@@ -234,6 +235,8 @@ def store_record_index(cloud_object, offsets, quotechar: str) -> dict:
     st, bucket = cloud_object.storage, cloud_object.meta_path.bucket
     meta = {"dataplug": __version__}
     attrs = {"record_index_key": key, "num_records": int(len(offsets)), "quotechar": quotechar}
+    if escapechar is not None:                           # the index honours an escape byte (include/dpquote.h)
+        attrs.update(escapechar=escapechar, escape_scope=escape_scope)
     if hasattr(offsets, "table"):
         bkey = key + ".blocks"
         st.put_object(Body=np.ascontiguousarray(offsets.low, "<u2").data, Bucket=bucket, Key=key, Metadata=meta)

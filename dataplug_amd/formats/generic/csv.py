@@ -15,6 +15,12 @@ Opt-in, beyond the reference: ``preprocess(extra_args={"quotechar": '"'})`` also
 ``record_index_format="u16b"`` (default ``"u64"``) stores the same record ends in a quarter of the bytes: uint16 low
 words at ``<key>.records`` and the 64 KiB block table at ``<key>.records.blocks``, both written by the kernel
 (attributes ``record_index_dtype``, ``record_index_blocks_key``, ``record_index_block0``); the strategies read either.
+``escapechar`` (with ``quotechar``; for example ``"\\\\"``) is for the dialect that writes a quote inside a field as
+``\\"`` (Spark, Hive, MySQL, ``csv.writer(escapechar=..., doublequote=False)``): the byte after an unescaped escape
+byte is literal, so an escaped quote does not open or close a field (include/dpquote.h).  ``escape_scope`` "all"
+(default; Python's csv module and pandas: the escape works outside quoted fields too, an escaped line break continues
+the record) or "quoted" (Spark / univocity: a line break outside a quoted field always ends the record).  The attributes
+``escapechar`` and ``escape_scope`` are stored, and ``CSVSlice.get_as_pandas`` parses with the stored dialect.
 """
 from __future__ import annotations
 
@@ -35,11 +41,20 @@ logger = logging.getLogger(__name__)
 
 def preprocess_csv(cloud_object: "CloudObject", separator: str = ",", line_index: bool = True,
                    index_format: str = "auto", quotechar: Optional[str] = None,
-                   record_index_format: str = "u64") -> PreprocessingMetadata:
+                   record_index_format: str = "u64", escapechar: Optional[str] = None,
+                   escape_scope: str = "all") -> PreprocessingMetadata:
     import pandas as pd
 
     if record_index_format not in ("u64", "u16b"):
         raise ValueError(f"record_index_format must be 'u64' or 'u16b', not {record_index_format!r}")
+    if escape_scope not in ("all", "quoted"):
+        raise ValueError(f"escape_scope must be 'all' or 'quoted', not {escape_scope!r}")
+    if escapechar is not None:
+        if quotechar is None:
+            raise ValueError("escapechar needs quotechar")
+        e = escapechar.encode("utf-8")
+        if len(e) != 1 or e == b"\n" or e == quotechar.encode("utf-8"):
+            raise ValueError(f"escapechar must be one byte other than the quote and a newline, not {escapechar!r}")
 
     top = []
     with cloud_object.open("r") as f:
@@ -47,12 +62,15 @@ def preprocess_csv(cloud_object: "CloudObject", separator: str = ",", line_index
             top.append(f.readline().strip())
         if quotechar is not None:
             # the sample must end at a record end: read on while it stops inside a quoted field
-            while sum(t.count(quotechar) for t in top) % 2 and len(top) < 4096:
+            while _open_quotes(top, quotechar, escapechar) and len(top) < 4096:
                 line = f.readline()
                 if not line:
                     break
                 top.append(line.strip())
-    df = pd.read_csv(io.StringIO("\n".join(top)), sep=separator, **({} if quotechar is None else {"quotechar": quotechar}))
+    dialect = {} if quotechar is None else {"quotechar": quotechar}
+    if escapechar is not None:
+        dialect["escapechar"] = escapechar
+    df = pd.read_csv(io.StringIO("\n".join(top)), sep=separator, **dialect)
     attrs = {"columns": df.columns.tolist(), "dtypes": df.dtypes.tolist()}
     if line_index:
         attrs.update(index_object(cloud_object, 0, index_format))
@@ -62,9 +80,27 @@ def preprocess_csv(cloud_object: "CloudObject", separator: str = ",", line_index
             raise ValueError(f"quotechar must be one byte other than a newline, not {quotechar!r}")
         from ...scan import objects as so
         kw = {} if record_index_format == "u64" else {"fmt": record_index_format}
+        if escapechar is not None:
+            kw.update(escape=escapechar.encode("utf-8")[0], escape_scope=escape_scope)
         attrs.update(store_record_index(cloud_object, so.record_index_object(cloud_object, quote=q[0], **kw),
-                                        quotechar))
+                                        quotechar, **({} if escapechar is None else
+                                                      {"escapechar": escapechar, "escape_scope": escape_scope})))
     return PreprocessingMetadata(attributes=attrs)
+
+
+def _open_quotes(lines, quotechar: str, escapechar: Optional[str]) -> int:
+    """1 iff the sample ``lines`` stop inside a quoted field: the parity of their quotes, the escaped ones left out."""
+    if escapechar is None:
+        return sum(t.count(quotechar) for t in lines) % 2
+    n = esc = 0
+    for ch in "\n".join(lines):
+        if esc:
+            esc = 0
+        elif ch == escapechar:
+            esc = 1
+        elif ch == quotechar:
+            n += 1
+    return n % 2
 
 
 @CloudDataFormat(preprocessing_function=preprocess_csv)
@@ -103,6 +139,10 @@ class CSVSlice(CloudObjectSlice):
 
     def get_as_pandas(self):
         import pandas as pd
+        attrs = self.cloud_object.attributes
+        esc = getattr(attrs, "escapechar", None) if attrs is not None else None
+        if esc:                                          # the dialect the record index was built for
+            return pd.read_csv(io.StringIO(self.get()), quotechar=attrs.quotechar, escapechar=esc)
         return pd.read_csv(io.StringIO(self.get()))
 
 

@@ -20,6 +20,11 @@ DQ_ERR_HIP = 2
 DQ_ERR_CAPACITY = 3
 DQ_ERR_OVERFLOW = 4
 DQ_ERR_TIMEOUT = 5
+DQ_ERR_ESCAPE_RUN = 6
+
+DQ_ESCAPE_RUN_MAX = 1 << 20              # include/dpquote.h: runs of escape bytes up to this many bytes are exact
+DQ_ESC_SCOPE_QUOTED = 1                  # flags bit of the escape-aware launches
+ESCAPE_SCOPES = {"all": 0, "quoted": DQ_ESC_SCOPE_QUOTED}
 
 # (name, restype, argtypes) for every symbol include/dpquote.h declares
 _c = ctypes
@@ -35,6 +40,11 @@ SIGNATURES = [
     ("dq_records_blocked_async", _c.c_int, [_p, _p, _u64, _u64, _u64, _u64, _c.c_uint32, _c.c_uint32, _p, _u64, _p,
                                             _u64]),
     ("dq_records_result",_c.c_int, [_p, _u64p, _u64p, _u64p]),
+    ("dq_records_esc_async", _c.c_int, [_p, _p, _u64, _u64, _u64, _u64, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                        _c.c_uint32, _c.c_uint32, _p, _c.c_int, _u64]),
+    ("dq_records_esc_blocked_async", _c.c_int, [_p, _p, _u64, _u64, _u64, _u64, _c.c_uint32, _c.c_uint32,
+                                                _c.c_uint32, _c.c_uint32, _c.c_uint32, _p, _u64, _p, _u64]),
+    ("dq_records_esc_result", _c.c_int, [_p, _u64p, _u64p, _u64p, _u64p]),
     ("dq_geometry", _c.c_int, [_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
 ]
 
@@ -70,6 +80,16 @@ def load(path: str = None):
     return lib
 
 
+class DPEscapeRunError(DPScanError):
+    """A run of escape bytes longer than DQ_ESCAPE_RUN_MAX: no index is returned (DQ_ERR_ESCAPE_RUN)."""
+
+
+def escape_flags(scope: str) -> int:
+    if scope not in ESCAPE_SCOPES:
+        raise ValueError(f"escape_scope must be 'all' or 'quoted', not {scope!r}")
+    return ESCAPE_SCOPES[scope]
+
+
 def last_error() -> str:
     return (load().dq_last_error() or b"").decode(errors="replace")
 
@@ -82,4 +102,6 @@ def check(rc: int) -> None:
         raise OverflowError(msg or "Python integer out of bounds for uint32")
     if rc == DQ_ERR_CAPACITY:
         raise DPCapacityError(rc, msg)
+    if rc == DQ_ERR_ESCAPE_RUN:
+        raise DPEscapeRunError(rc, msg)
     raise DPScanError(rc, msg)

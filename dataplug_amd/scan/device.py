@@ -501,6 +501,91 @@ class ScanContext:
                 continue
             return self.d2h(np.empty(n, np.uint16), out.ptr), self.d2h(np.empty(nt, np.uint64), tab.ptr), nq, nn
 
+    # ---------------------------------------------------------------- ... with an escape byte (dq_records_esc_*)
+    def record_ends_escaped_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int,
+                                  carry: int, escape: int, esc_carry: int, scope: str, d_out: int, u64: bool,
+                                  cap: int) -> None:
+        from . import _quote
+        q, h = self._quote_ctx()
+        _quote.check(q.dq_records_esc_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote),
+                                            int(carry), int(escape), int(esc_carry), _quote.escape_flags(scope),
+                                            ctypes.c_void_p(d_out or 0), int(u64), int(cap)))
+
+    def record_ends_escaped_result(self) -> Tuple[int, int, int, int]:
+        """(record ends, quote bytes, newlines, toggles) of the launch in flight: ``toggles`` are the quote bytes
+        that are not escaped; DPCapacityError carries ``needed``, a run of escape bytes beyond DQ_ESCAPE_RUN_MAX
+        raises ``_quote.DPEscapeRunError``."""
+        from . import _quote
+        q, h = self._quote_ctx()
+        n, nq, nn, nt = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = q.dq_records_esc_result(h, ctypes.byref(n), ctypes.byref(nq), ctypes.byref(nn), ctypes.byref(nt))
+        if rc == _quote.DQ_ERR_CAPACITY:
+            e = DPCapacityError(rc, _quote.last_error())
+            e.needed, e.n_quotes, e.n_newlines, e.n_toggles = int(n.value), int(nq.value), int(nn.value), \
+                int(nt.value)
+            raise e
+        _quote.check(rc)
+        return int(n.value), int(nq.value), int(nn.value), int(nt.value)
+
+    def record_counts_escaped(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
+                              carry: int = 0, escape: int = 92, esc_carry: int = 0,
+                              scope: str = "all") -> Tuple[int, int, int, int]:
+        """The count-only launch with an escape byte: (record ends, quote bytes, newlines, toggles)."""
+        self.record_ends_escaped_async(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry, scope,
+                                       0, True, 0)
+        return self.record_ends_escaped_result()
+
+    def record_ends_escaped(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
+                            carry: int = 0, escape: int = 92, esc_carry: int = 0, scope: str = "all",
+                            u64: bool = True, cap: Optional[int] = None):
+        """``record_ends`` for the dialect that escapes a quote inside a field with ``escape`` (include/dpquote.h:
+        a byte after an unescaped escape byte is literal; ``esc_carry`` = the byte at ``begin`` is escaped; ``scope``
+        "all" or "quoted").  Returns (offsets uint64|uint32, quote bytes seen, newlines seen, toggles)."""
+        dtype = np.uint64 if u64 else np.uint32
+        if cap is None:
+            cap = (end - begin) // 16 + 1024
+        while True:
+            out = self.workspace("out", cap * np.dtype(dtype).itemsize + 16)
+            self.record_ends_escaped_async(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry,
+                                           scope, out.ptr, u64, cap)
+            try:
+                n, nq, nn, nt = self.record_ends_escaped_result()
+            except DPCapacityError as e:
+                cap = e.needed
+                continue
+            return self.d2h(np.empty(n, dtype), out.ptr), nq, nn, nt
+
+    def record_ends_blocked_escaped_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int,
+                                          quote: int, carry: int, escape: int, esc_carry: int, scope: str,
+                                          d_low: int, cap: int, d_table: int, table_cap: int) -> None:
+        from . import _quote
+        q, h = self._quote_ctx()
+        _quote.check(q.dq_records_esc_blocked_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end,
+                                                    int(quote), int(carry), int(escape), int(esc_carry),
+                                                    _quote.escape_flags(scope), ctypes.c_void_p(d_low or 0),
+                                                    int(cap), ctypes.c_void_p(d_table or 0), int(table_cap)))
+
+    def record_ends_blocked_escaped(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int,
+                                    quote: int = 34, carry: int = 0, escape: int = 92, esc_carry: int = 0,
+                                    scope: str = "all", cap: Optional[int] = None):
+        """``record_ends_blocked`` with an escape byte: (low uint16, table uint64, quote bytes seen, newlines seen,
+        toggles)."""
+        if cap is None:
+            cap = (end - begin) // 16 + 1024
+        nt = self.record_block_tiles(begin, end)
+        while True:
+            out = self.workspace("out", cap * 2 + 16)
+            tab = self.workspace("record_blocks", nt * 8 + 16)
+            self.record_ends_blocked_escaped_async(d_buf, buf_len, buf_base, begin, end, quote, carry, escape,
+                                                   esc_carry, scope, out.ptr, cap, tab.ptr, nt)
+            try:
+                n, nq, nn, ntog = self.record_ends_escaped_result()
+            except DPCapacityError as e:
+                cap = e.needed
+                continue
+            return self.d2h(np.empty(n, np.uint16), out.ptr), self.d2h(np.empty(nt, np.uint64), tab.ptr), nq, nn, \
+                ntog
+
     def find_delim(self, d_buf: int, buf_len: int, buf_base: int, start: int, delim: int = 10) -> int:
         """First object offset >= start holding ``delim`` in the buffer, or -1."""
         pos = ctypes.c_int64(-1)

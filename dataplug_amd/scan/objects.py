@@ -617,8 +617,29 @@ def line_index_object(co, begin: int = 0, end: Optional[int] = None, delim: int 
     return BlockedOffsets(low, table, merge.J0)
 
 
+def escape_carry_at(co, begin: int, lo: int, escape: int) -> int:
+    """1 iff object byte ``lo`` is escaped in a scan that starts at ``begin``: the parity of the run of ``escape``
+    bytes that ends right before ``lo``.  Small ranged GETs of the bytes before ``lo``, walking back only while
+    they are all escape bytes; a run beyond DQ_ESCAPE_RUN_MAX raises ``DPEscapeRunError`` like the kernel's walk."""
+    from ._quote import DQ_ERR_ESCAPE_RUN, DQ_ESCAPE_RUN_MAX, DPEscapeRunError
+    run, hi, step = 0, lo, 64
+    while hi > begin:
+        a = max(begin, hi - step)
+        raw = co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key, Range=f"bytes={a}-{hi - 1}")["Body"].read()
+        tail = len(raw) - len(raw.rstrip(bytes([escape])))
+        run += tail
+        if tail < len(raw):
+            break
+        if run > DQ_ESCAPE_RUN_MAX:
+            raise DPEscapeRunError(DQ_ERR_ESCAPE_RUN, f"a run of escape bytes longer than {DQ_ESCAPE_RUN_MAX} "
+                                                      f"before object offset {lo}")
+        hi, step = a, min(step * 16, 1 << 20)
+    return run & 1
+
+
 def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: int = 34,
-                        max_devices: Optional[int] = None, part_bytes: int = 8 << 30, fmt: str = "u64"):
+                        max_devices: Optional[int] = None, part_bytes: int = 8 << 30, fmt: str = "u64",
+                        escape: Optional[int] = None, escape_scope: str = "all"):
     """Sorted offsets of the record ends of object bytes [begin, end): the '\\n' bytes outside quoted fields
     (an even number of ``quote`` bytes between ``begin`` and the newline; include/dpquote.h).  ``fmt`` "u64": a
     uint64 array; "u16b": a ``BlockedOffsets`` (uint16 low words + the 64 KiB block table, both written by the
@@ -627,9 +648,19 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
     The parts come from ``line_parts`` and run round-robin on the GPUs like a newline index.  A part does not know
     whether it starts inside a quoted field, so it runs two launches on its resident bytes: a count-only one that
     yields its number of quote bytes, and -- once the counts of every part before it are in, chained on the host
-    into the part's incoming state -- the emitting one.  The second read is of HBM, not of the storage."""
+    into the part's incoming state -- the emitting one.  The second read is of HBM, not of the storage.
+
+    ``escape``: the byte that makes the next byte literal (include/dpquote.h; ``escape_scope`` "all" or "quoted"), for
+    objects that write a quote inside a field as ``\\"``.  Whether a part's first byte is escaped is read from the
+    object itself (``escape_carry_at``: nothing from other parts, so the count launch still runs at once), and the
+    chain adds up the parts' toggles -- their quotes that are not escaped -- in place of their quote bytes."""
     if fmt not in ("u64", "u16b"):
         raise ValueError(f"record index format must be 'u64' or 'u16b', not {fmt!r}")
+    if escape is not None:
+        from ._quote import escape_flags
+        escape_flags(escape_scope)
+        if not 0 <= escape <= 255 or escape in (quote, 10):
+            raise ValueError("escape must be a byte other than the quote and '\\n'")
     end = co.size if end is None else end
     if end <= begin:
         return np.zeros(0, np.uint64) if fmt == "u64" else \
@@ -648,7 +679,12 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
         d = ctx.workspace("input", n + 64, placed=True)
         dp = d.ptr + (lo & 15)
         fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
-        n_rec, quotes[k], _ = ctx.record_counts(dp, n, lo, lo, hi, quote=quote, carry=0)
+        if escape is None:
+            n_rec, quotes[k], _ = ctx.record_counts(dp, n, lo, lo, hi, quote=quote, carry=0)
+        else:
+            ec = escape_carry_at(co, begin, lo, escape) if k else 0
+            n_rec, _, _, quotes[k] = ctx.record_counts_escaped(dp, n, lo, lo, hi, quote=quote, carry=0, escape=escape,
+                                                               esc_carry=ec, scope=escape_scope)
         counted[k].set()
         for j in range(k):                               # parts before this one: on this worker done, on others
             while not counted[j].wait(0.05):             # at least counted before they wait for anything
@@ -657,7 +693,14 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
         carry = sum(quotes[:k]) & 1
         # the count under carry 0 bounds nothing under carry 1: size the output by the newlines only on a retry
         cap = max(n_rec, 1) if carry == 0 else None
-        if fmt == "u16b":                                # dp is congruent to lo mod 16: the blocked form's grid
+        if escape is not None:
+            if fmt == "u16b":
+                out[k] = ctx.record_ends_blocked_escaped(dp, n, lo, lo, hi, quote=quote, carry=carry, escape=escape,
+                                                         esc_carry=ec, scope=escape_scope, cap=cap)[:2]
+            else:
+                out[k] = ctx.record_ends_escaped(dp, n, lo, lo, hi, quote=quote, carry=carry, escape=escape,
+                                                 esc_carry=ec, scope=escape_scope, u64=True, cap=cap)[0]
+        elif fmt == "u16b":                              # dp is congruent to lo mod 16: the blocked form's grid
             out[k] = ctx.record_ends_blocked(dp, n, lo, lo, hi, quote=quote, carry=carry, cap=cap)[:2]
         else:
             out[k] = ctx.record_ends(dp, n, lo, lo, hi, quote=quote, carry=carry, u64=True, cap=cap)[0]

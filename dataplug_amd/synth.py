@@ -129,9 +129,24 @@ def csv_quoted(size: int, seed: int = 0) -> np.ndarray:
     """``csv`` rows with an 11th column ``Note``: empty, plain, or RFC 4180 quoted text holding line breaks, commas
     and escaped quotes (``""``).  Exactly ``size`` bytes, valid RFC 4180, deterministic, ends with a record end (the
     last row's note is padded to fit)."""
+    return _csv_noted(size, seed, _NOTES, "csv_quoted")
+
+
+# the notes of csv_quoted in the dialect that escapes: \" for a quote, \\ for the escape byte itself
+_NOTES_ESCAPED = [n.replace(b'""', b'\\"') for n in _NOTES] + [b"a back\\\\slash", b"C:\\\\dir\\\\", b"odd \\\\\\\"run"]
+
+
+def csv_escaped(size: int, seed: int = 0) -> np.ndarray:
+    """``csv_quoted`` in the dialect of Spark, Hive and ``csv.writer(escapechar='\\\\', doublequote=False)``: a quote
+    inside a quoted note is written ``\\"`` and a backslash ``\\\\`` (some notes end in one, right before the closing
+    quote).  Exactly ``size`` bytes, deterministic, ends with a record end."""
+    return _csv_noted(size, seed, _NOTES_ESCAPED, "csv_escaped")
+
+
+def _csv_noted(size: int, seed: int, notes, name: str) -> np.ndarray:
     head = CSV_HEADER[:-1] + b",Note\n"
     if size < len(head) + 128:
-        raise ValueError(f"csv_quoted needs at least {len(head) + 128} bytes")
+        raise ValueError(f"{name} needs at least {len(head) + 128} bytes")
     rng = np.random.default_rng(seed)
     rows = [head]
     total = len(head)
@@ -141,7 +156,7 @@ def csv_quoted(size: int, seed: int = 0) -> np.ndarray:
         ci = rng.integers(0, len(_CITIES), m)
         kind = rng.integers(0, 4, m)                      # 0 empty, 1 plain, 2-3 quoted
         nfrag = rng.integers(1, 5, m)
-        frag = rng.integers(0, len(_NOTES), (m, 4))
+        frag = rng.integers(0, len(notes), (m, 4))
         for j in range(m):
             base = b"%d,%d,%d,N,%d,%d,%d,W,%s," % (v[j, 0] % 50 + 25, v[j, 1], v[j, 2], v[j, 3] + 60, v[j, 4], v[j, 5],
                                                    _CITIES[ci[j]])
@@ -150,7 +165,7 @@ def csv_quoted(size: int, seed: int = 0) -> np.ndarray:
             elif kind[j] == 1:
                 note = b"plain note"
             else:
-                note = b'"' + b" ".join(_NOTES[f] for f in frag[j, :nfrag[j]]) + b'"'
+                note = b'"' + b" ".join(notes[f] for f in frag[j, :nfrag[j]]) + b'"'
             r = base + note + b"\n"
             if size - total - len(r) < 128:               # the last row: a quoted note padded to the exact size
                 rows.append(base + b'"' + b"x" * (size - total - len(base) - 3) + b'"\n')

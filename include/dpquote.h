@@ -13,6 +13,30 @@
  * is a RECORD END iff P(p) == 0.  An escaped quote "" toggles twice, so the parity rule is exact for
  * RFC 4180 input; for malformed input the parity rule is the definition.
  *
+ * Escape-aware semantics (dq_records_esc_async, dq_records_esc_blocked_async): the dialect that writes a quote
+ * inside a field as \" (Spark, Hive, MySQL INTO OUTFILE, Python csv with escapechar and doublequote=False).  With an
+ * escape byte e (e != q, e != '\n') and an incoming esc_carry (1 = "the byte at begin is escaped"):
+ *
+ *     esc = esc_carry; inside = carry; toggles = 0
+ *     for p in begin .. end-1:
+ *         b = d[p]
+ *         if esc:                      an escaped byte is literal, whatever it is (an escape byte included)
+ *             esc = 0
+ *             if b == '\n' and not inside and scope == QUOTED: record end at p
+ *             continue
+ *         if   b == e: esc = 1
+ *         elif b == q: inside ^= 1; toggles += 1
+ *         elif b == '\n' and not inside: record end at p
+ *
+ * A byte is escaped iff it follows a maximal run of not-escaped escape bytes of odd length.  Escaped quotes do not
+ * toggle; "" still toggles twice.  Scope ALL (flags = 0, what Python's csv module and pandas do): the escape works
+ * outside quoted fields too, an escaped '\n' never ends a record.  Scope QUOTED (DQ_ESC_SCOPE_QUOTED, what Spark /
+ * univocity files need): a '\n' outside a quoted field always ends the record, so an unquoted field may end in the
+ * escape byte.  On malformed input this state machine is the definition.
+ * Runs of escape bytes up to DQ_ESCAPE_RUN_MAX bytes are exact.  A longer run may end the launch with
+ * DQ_ERR_ESCAPE_RUN (the kernel walks back over a run only so far; it waits for nothing and never returns a wrong
+ * index instead).
+ *
  * Reference interface this stands in for (CLOUDLAB-URV/dataplug @ 2025-07-11): the row boundaries that
  * CSVSlice.get resolves byte by byte (formats/generic/csv.py:52-105).  The reference treats every '\n' as
  * a row end there, which cuts RFC 4180 records whose quoted fields hold line breaks; this index is the
@@ -34,6 +58,10 @@ extern "C" {
 #define DQ_ERR_CAPACITY 3  /* output capacity too small; the required count is still returned */
 #define DQ_ERR_OVERFLOW 4  /* a uint32 offset would be >= 2^32 */
 #define DQ_ERR_TIMEOUT 5   /* an inter-workgroup wait hit its bound (results invalid) */
+#define DQ_ERR_ESCAPE_RUN 6 /* a run of escape bytes longer than DQ_ESCAPE_RUN_MAX (results invalid) */
+
+#define DQ_ESCAPE_RUN_MAX (1u << 20) /* runs of escape bytes up to this many bytes are exact */
+#define DQ_ESC_SCOPE_QUOTED 1u       /* flags bit: the escape works inside quoted fields only */
 
 typedef struct dq_ctx dq_ctx;
 
@@ -88,6 +116,31 @@ int dq_records_blocked_async(dq_ctx* ctx, const uint8_t* d_buf, uint64_t buf_len
  *   DQ_ERR_TIMEOUT:  a look-back wait exceeded its 20 s bound; the kernel ended, the output is invalid.
  */
 int dq_records_result(dq_ctx* ctx, uint64_t* n_out, uint64_t* n_quotes, uint64_t* n_newlines);
+
+/*
+ * The escape-aware launches (additive entry points of ABI version 1; further instantiations of the same kernel).
+ * Arguments as dq_records_async / dq_records_blocked_async, plus: escape, the escape byte; esc_carry, 0 or 1, 1 = the
+ * byte at `begin` is escaped; flags, 0 (scope ALL) or DQ_ESC_SCOPE_QUOTED.  At most one launch of any kind is in
+ * flight per ctx; collect with dq_records_esc_result (or dq_records_result).
+ * DQ_ERR_INVALID: escape > 255, escape == quote, escape == '\n', esc_carry > 1, an unknown flags bit, and every check
+ *   of the entry point they extend.
+ */
+int dq_records_esc_async(dq_ctx* ctx, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base, uint64_t begin,
+                         uint64_t end, uint32_t quote, uint32_t carry, uint32_t escape, uint32_t esc_carry,
+                         uint32_t flags, void* d_out, int out_u64, uint64_t cap);
+int dq_records_esc_blocked_async(dq_ctx* ctx, const uint8_t* d_buf, uint64_t buf_len, uint64_t buf_base,
+                                 uint64_t begin, uint64_t end, uint32_t quote, uint32_t carry, uint32_t escape,
+                                 uint32_t esc_carry, uint32_t flags, uint16_t* d_low, uint64_t cap,
+                                 uint64_t* d_table, uint64_t table_cap);
+/*
+ * dq_records_result plus *n_toggles: the quote bytes that are not escaped, which is what a chain of launches over
+ * consecutive ranges adds up into the next range's carry (for a plain launch: n_quotes).  After an escape-aware
+ * launch *n_quotes still counts every byte == quote; *n_newlines counts the '\n' bytes that can end a record: all
+ * of them under scope QUOTED, the ones that are not escaped under scope ALL.
+ *   DQ_ERR_ESCAPE_RUN: a run of escape bytes longer than DQ_ESCAPE_RUN_MAX; the kernel ended, the output is invalid.
+ */
+int dq_records_esc_result(dq_ctx* ctx, uint64_t* n_out, uint64_t* n_quotes, uint64_t* n_newlines,
+                          uint64_t* n_toggles);
 
 /* Launch geometry (for tests/tuning): workgroups of the persistent grid, and bytes per tile. */
 int dq_geometry(dq_ctx* ctx, int* grid, int* tile_bytes);

@@ -20,6 +20,14 @@ blocked=True)`` / ``prepare(..., blocked=True)`` lay the tiles on the object's 6
 offset begin & ~0xFFFF, lo up to 65535), and ``finish(..., fmt="u16b")`` / ``run(..., fmt="u16b")`` return
 ``(low, table, n_out, n_quotes, n_newlines, err_bits)``: the uint16 low words and the block table (each tile's
 exclusive base).  ``BLOCKED_MUTANTS`` are the deliberate defects of that code; tests/test_quote_blocked_model.py.
+
+The escape-aware instantiations (quote_kernel<.., 1>, dq_records_esc_async / dq_records_esc_blocked_async) are asked
+for by keyword too: ``prepare(..., escape=92, esc_carry=0, escape_scope="all")`` / ``run(...)`` with the same
+keywords model the escape mask, the add-carry escaped mask (``esc_code``), the two ballots per row (all-escape chunks,
+trailing-run parity), the scalar row chain, the wave's walk back over the chunks before it with its bound
+(``ERR_ESCAPE_RUN``) and ``esc_carry`` applied at the byte ``lo``.  The result tuples keep their shape; the number of
+unescaped quotes is ``Prepared.n_toggles`` and ``stats["n_toggles"]``.  ``ESCAPE_MUTANTS`` are the deliberate defects
+of that code; tests/test_quote_escape_model.py.
 """
 from __future__ import annotations
 
@@ -48,7 +56,13 @@ STAT_AGG, STAT_PREFIX = 1 << STATUS_SHIFT, 2 << STATUS_SHIFT
 ERR_TIMEOUT, ERR_OVERFLOW = 1, 2          # the kernel's bits of the error word
 ERR_CAPACITY = 4                          # the model's bit for dq_records_result's check n_out > cap
 ERR_STRAY = 8                             # the model's bit for a store beyond every newline (only a mutant does it)
+ERR_ESCAPE_RUN = 16                       # the model's bit for the kernel's kErrEscapeRun (its bit 4 is taken above)
 MAX_TILES = 0xFFFF0000
+
+ODD_BITS = 0xAAAAAAAA
+ESCAPE_RUN_MAX = 1 << 20                  # include/dpquote.h DQ_ESCAPE_RUN_MAX
+ESC_WINDOWS = ESCAPE_RUN_MAX // (WAVE * 16)
+ESC_SCOPE_QUOTED = 1
 
 MUTANTS = ("then_swapped", "window_drops_f", "base_swapped", "ignore_carry", "no_run", "valid_hi_plus_one",
            "unsigned_dot", "agg_k1_shift16")
@@ -56,14 +70,19 @@ MUTANTS = ("then_swapped", "window_drops_f", "base_swapped", "ignore_carry", "no
 # deliberate defects of the blocked form only (they change nothing in the uint32 / uint64 forms)
 BLOCKED_MUTANTS = ("table_inclusive", "low_from_shifted", "table_skip_tile0")
 
+# deliberate defects of the escape-aware code only (they change nothing without ``escape=``)
+ESCAPE_MUTANTS = ("escaped_quote_toggles", "all_escape_resets", "esc_carry_at_chunk_start", "wave_flag_zero",
+                  "all_keeps_escaped_newlines")
+
 M32 = 0xFFFFFFFF
 M64 = (1 << 64) - 1
 CANARY = 0xEEEEEEEEEEEEEEEE
 
 
 def _check_mutant(mutate):
-    if mutate is not None and mutate not in MUTANTS and mutate not in BLOCKED_MUTANTS:
-        raise ValueError(f"mutate={mutate!r}: one of {MUTANTS + BLOCKED_MUTANTS}")
+    if mutate is not None and mutate not in MUTANTS and mutate not in BLOCKED_MUTANTS and \
+            mutate not in ESCAPE_MUTANTS:
+        raise ValueError(f"mutate={mutate!r}: one of {MUTANTS + BLOCKED_MUTANTS + ESCAPE_MUTANTS}")
 
 
 # ------------------------------------------------------------------------------------------ instructions
@@ -132,6 +151,84 @@ def mbcnt(pred: np.ndarray) -> np.ndarray:
 def popcll_ballot(pred: np.ndarray) -> np.ndarray:
     """popcll(ballot(pred)): wave-uniform, the lane axis dropped."""
     return pred.astype(np.int64).sum(-1)
+
+
+# ------------------------------------------------------------------------------------------ escape bytes
+def esc_code(e: np.ndarray, inb: np.ndarray) -> np.ndarray:
+    """esc_code of escape masks ``e`` and entry bits ``inb`` (32-bit arithmetic): with c the result, the escaped bytes
+    are (c ^ (e | inb)) & 0xFFFF and bit 15 of c & e says that the byte after the chunk is escaped."""
+    e, inb = np.asarray(e, np.int64), np.asarray(inb, np.int64)
+    pot = e & ~inb & M32
+    return ((((pot << 1) & M32) | ODD_BITS) - pot) & M32 ^ ODD_BITS
+
+
+def esc_chunks(e: np.ndarray, x: np.ndarray, lo: int, esc_carry: int, mutate: Optional[str] = None):
+    """esc_chunk of chunks at coordinates ``x`` with (valid) escape masks ``e``: (first, in0, a, t)."""
+    first = (x <= lo) & (lo < x + 16)
+    at = 0 if mutate == "esc_carry_at_chunk_start" else np.where(first, lo - x, 0)
+    in0 = np.where(first, (esc_carry << at) & M32, 0)
+    a = (e == 0xFFFF) & ~first
+    if mutate == "all_escape_resets":
+        a = np.zeros_like(a)
+    t = ((esc_code(e, in0) & e) >> 15) & 1
+    return first, in0, a, t
+
+
+def wave_esc_in(a_flat: np.ndarray, t_flat: np.ndarray, xw: int, lo: int, hi: int, mutate: Optional[str] = None):
+    """wave_esc_in of the wave that starts at coordinate ``xw``: (is its first byte escaped, error).  ``a_flat`` and
+    ``t_flat`` are the a / t bits of every chunk of the launch by chunk index (chunks the kernel does not load: 0)."""
+    if xw <= lo or xw >= hi or mutate == "wave_flag_zero":
+        return 0, 0
+    c0 = xw >> 4
+    lanes = np.arange(WAVE)
+    it = 0
+    while True:
+        idx = c0 - (it * WAVE + lanes + 1)               # back <= xw  <=>  idx >= 0
+        ok = idx >= 0
+        ca = np.where(ok, a_flat[np.where(ok, idx, 0)], 0)
+        ct = np.where(ok, t_flat[np.where(ok, idx, 0)], 0)
+        if it == ESC_WINDOWS:
+            return (0, 1) if ca[0] else (int(ct[0]), 0)
+        stop = np.nonzero(ca == 0)[0]
+        if len(stop):
+            return int(ct[stop[0]]), 0                   # ctz of ~ba: the nearest chunk that is not all escape bytes
+        it += 1
+
+
+def escape_phase(e, x, q, n, a: "Args", mutate: Optional[str] = None):
+    """The escape-aware part of phase A over every chunk ([tiles, waves, rows, lanes]): the quote and newline masks
+    with the escaped bytes taken out, the raw quote counts, and the error flag of the walk back."""
+    T = e.shape[0]
+    first, in0, ca, ct = esc_chunks(e, x, a.lo, a.esc_carry, mutate)
+    a_flat, t_flat = ca.reshape(-1).astype(np.int64), ct.reshape(-1).astype(np.int64)
+    erow = np.zeros((T, WAVES), np.int64)
+    err = 0
+    # a wave walks back only if the chunk before it is all escape bytes: the others read their flag off that chunk
+    for t in range(T):
+        for w in range(WAVES):
+            erow[t, w], bad = wave_esc_in(a_flat, t_flat, t * TILE_BYTES + w * WAVE_BYTES, a.lo, a.hi, mutate)
+            err |= bad
+    lanes = np.arange(WAVE)
+    inb = np.zeros_like(e)
+    for r in range(ROWS):
+        na = ~ca[:, :, r, :].astype(bool)                # lanes that are not all escape bytes
+        # highest lane below each lane that is not all-escape (63 - clzll(stop)), -1 for none
+        cand = np.where(na, lanes, -1)
+        upto = np.maximum.accumulate(cand, axis=-1)      # highest such lane <= each lane
+        below = np.concatenate([np.full(upto.shape[:-1] + (1,), -1), upto[..., :-1]], axis=-1)
+        tr = ct[:, :, r, :]
+        chain = np.where(below >= 0, np.take_along_axis(tr, np.maximum(below, 0), axis=-1), erow[:, :, None])
+        inb[:, :, r, :] = chain
+        top = upto[..., -1]
+        erow = np.where(top >= 0, np.take_along_axis(tr, np.maximum(top, 0)[..., None], axis=-1)[..., 0], erow)
+    inb = np.where(first, in0, inb)
+    escaped = (esc_code(e, inb) ^ (e | inb)) & 0xFFFF
+    raw = popc(q)
+    if mutate != "escaped_quote_toggles":
+        q = q & ~escaped
+    nl_mask = 0 if mutate == "all_keeps_escaped_newlines" else a.esc_nl
+    n = n & ~(escaped & nl_mask)
+    return q, n, raw, err
 
 
 # ------------------------------------------------------------------------------------------ summaries, descriptors
@@ -301,10 +398,22 @@ class Args:
     ntiles: int
     key_q: int
     key_nl: int
+    key_e: int = 0                   # the escape-aware launches (``escape`` is None otherwise)
+    esc_carry: int = 0
+    esc_nl: int = 0
+    escape: Optional[int] = None
 
 
 def host_args(dev_addr: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
-              blocked: bool = False) -> Args:
+              blocked: bool = False, escape: Optional[int] = None, esc_carry: int = 0,
+              escape_scope: str = "all") -> Args:
+    if escape is not None:
+        if not 0 <= escape <= 255 or escape == 10 or escape == quote:
+            raise ValueError("escape must be a byte other than the quote and '\\n'")
+        if esc_carry not in (0, 1):
+            raise ValueError("esc_carry must be 0 or 1")
+        if escape_scope not in ("all", "quoted"):
+            raise ValueError("escape_scope must be 'all' or 'quoted'")
     if begin > end or begin < buf_base or end - buf_base > buf_len:
         raise ValueError("[begin, end) outside the buffer")
     if not 0 <= quote <= 255 or quote == 10:
@@ -323,8 +432,12 @@ def host_args(dev_addr: int, buf_len: int, buf_base: int, begin: int, end: int, 
         ntiles = (shift + n + TILE_BYTES - 1) // TILE_BYTES if n else 0
     if ntiles >= MAX_TILES:
         raise ValueError("range too large for one launch")
+    if escape is None:
+        return Args(p - shift, shift, shift, shift + n, obj0, ntiles,
+                    ((quote * 0x01010101) & M32) ^ SEL12, 0x0A0A0A0A ^ SEL12)
     return Args(p - shift, shift, shift, shift + n, obj0, ntiles,
-                ((quote * 0x01010101) & M32) ^ SEL12, 0x0A0A0A0A ^ SEL12)
+                ((quote * 0x01010101) & M32) ^ SEL12, 0x0A0A0A0A ^ SEL12,
+                ((escape * 0x01010101) & M32) ^ SEL12, esc_carry, 0xFFFF if escape_scope == "all" else 0, escape)
 
 
 @dataclass
@@ -340,6 +453,8 @@ class Prepared:
     n_quotes: int = 0
     n_newlines: int = 0
     blocked: bool = False            # tiles on the object's 64 KiB grid (quote_kernel<2>)
+    n_toggles: int = 0               # escape-aware launches: the quotes that are not escaped (else n_quotes)
+    esc_err: int = 0                 # escape-aware launches: the walk back met a run beyond ESCAPE_RUN_MAX
 
 
 def launch_memory(buf: np.ndarray, dev_addr: int, a: Args, outside: bytes) -> np.ndarray:
@@ -361,14 +476,15 @@ def launch_memory(buf: np.ndarray, dev_addr: int, a: Args, outside: bytes) -> np
 
 def prepare(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = None, end: Optional[int] = None,
             quote: int = 34, mutate: Optional[str] = None, outside: bytes = b'"\n',
-            blocked: bool = False) -> Prepared:
+            blocked: bool = False, escape: Optional[int] = None, esc_carry: int = 0,
+            escape_scope: str = "all") -> Prepared:
     """Host arithmetic, phase A and the tile summaries of one launch over ``buf`` (the buffer's bytes, object bytes
     [buf_base, buf_base + len(buf))) placed at device address ``dev_addr``; only dev_addr mod 16 matters."""
     _check_mutant(mutate)
     buf = np.asarray(buf, np.uint8)
     begin = buf_base if begin is None else begin
     end = buf_base + len(buf) if end is None else end
-    a = host_args(dev_addr, len(buf), buf_base, begin, end, quote, blocked)
+    a = host_args(dev_addr, len(buf), buf_base, begin, end, quote, blocked, escape, esc_carry, escape_scope)
     T = a.ntiles
     shape = (T, WAVES, ROWS, WAVE)
     if T == 0:
@@ -381,6 +497,9 @@ def prepare(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = No
     ok = np.where(loaded, valid16(np.where(loaded, x, a.lo), a.lo, a.hi, mutate), 0)
     q = mask16(v, a.key_q, mutate) & ok
     n = mask16(v, a.key_nl, mutate) & ok
+    raw, esc_err = None, 0
+    if a.escape is not None:
+        q, n, raw, esc_err = escape_phase(mask16(v, a.key_e, mutate) & ok, x, q, n, a, mutate)
     px = q.copy()
     for s in (1, 2, 4, 8):
         px ^= (px << s) & M32
@@ -394,6 +513,8 @@ def prepare(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = No
     cnt = (popc(k0) | (popc(k1) << 16)).sum(2) & M32     # per lane over the rows
     cnt = cnt.sum(-1) & M32                              # wave_sum
     nq = popc(q).sum(2).sum(-1) & M32
+    if raw is not None:                                  # packed per lane: the quote bytes << 16 | the unescaped ones
+        nq = (nq + ((raw.sum(2).sum(-1) << 16) & M32)) & M32
     P = Prepared(a, mutate, km, row_par.sum(-1) & 1, cnt & 0xFFFF, cnt >> 16, nq, blocked=blocked)
     for t in range(T):
         s = IDENT
@@ -401,6 +522,9 @@ def prepare(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = No
             s = then(s, Sum(int(P.wpar[t, w]), int(P.wk0[t, w]), int(P.wk1[t, w])))
         P.tiles.append(s)
     P.n_quotes = int(P.wq.sum())                         # the atomicAdds of tq and tn
+    P.n_toggles = P.n_quotes
+    if raw is not None:                                  # wave 0 unpacks the halves before it adds the waves up
+        P.n_quotes, P.n_toggles, P.esc_err = int((P.wq >> 16).sum()), int((P.wq & 0xFFFF).sum()), esc_err
     P.n_newlines = int((P.wk0 + P.wk1).sum())
     return P
 
@@ -521,8 +645,10 @@ def finish(P: Prepared, carry: int = 0, u64: bool = True, cap: Optional[int] = N
         err |= ERR_CAPACITY
     if stray:
         err |= ERR_STRAY
+    if P.esc_err:
+        err |= ERR_ESCAPE_RUN
     if stats is not None:
-        stats.update(st, out_raw=out, state_in=state_in, base=base)
+        stats.update(st, out_raw=out, state_in=state_in, base=base, n_toggles=P.n_toggles)
     if u16b:
         table = np.full(P.args.ntiles + 8, CANARY, np.uint64)
         table_stores(P, state_in, base, table, mutate)
@@ -535,11 +661,11 @@ def finish(P: Prepared, carry: int = 0, u64: bool = True, cap: Optional[int] = N
 def run(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = None, end: Optional[int] = None,
         quote: int = 34, carry: int = 0, u64: bool = True, cap: Optional[int] = None, schedule="sequential",
         mutate: Optional[str] = None, outside: bytes = b'"\n', stats: Optional[dict] = None,
-        fmt: Optional[str] = None):
+        fmt: Optional[str] = None, escape: Optional[int] = None, esc_carry: int = 0, escape_scope: str = "all"):
     """One launch, as ScanContext.record_ends_async + record_ends_result see it:
     (offsets, n_out, n_quotes, n_newlines, err_bits); with ``fmt="u16b"`` as record_ends_blocked_async does:
     (low, table, n_out, n_quotes, n_newlines, err_bits)."""
     if fmt not in (None, "u16b"):
         raise ValueError(f"fmt={fmt!r}: None (the uint32 / uint64 forms, by u64=) or 'u16b'")
-    return finish(prepare(buf, dev_addr, buf_base, begin, end, quote, mutate, outside, fmt == "u16b"), carry, u64,
-                  cap, schedule, mutate, stats, fmt)
+    return finish(prepare(buf, dev_addr, buf_base, begin, end, quote, mutate, outside, fmt == "u16b", escape,
+                          esc_carry, escape_scope), carry, u64, cap, schedule, mutate, stats, fmt)

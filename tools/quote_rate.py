@@ -8,6 +8,8 @@ process, alternating launch by launch after a warm-up of each:
 * ``dq_records_async`` (uint64 output), HIP events on the context stream around the whole call: the per-launch
   zeroing of the descriptors, the kernel and the 64-byte result copy;
 * ``dq_records_blocked_async`` (u16b: uint16 low words + the 64 KiB block table), timed the same way;
+* ``dq_records_esc_async`` (uint64 output, the escape-aware instantiation) on the same buffer with an escape byte that
+  does not occur in it, so only the extra work is timed, and on a second buffer of ``synth.csv_escaped`` blocks;
 * ``dp_stream_read``, the read-only calibration kernel, and ``dp_delim_index`` (uint64), the newline index, each timed
   by the library's own HIP events around its kernels (dp_timing_enable).
 Prints one JSON line: the times and GiB/s (input bytes over time), the ratio of each record-index form's rate to the
@@ -64,6 +66,23 @@ def model_ends(d: np.ndarray) -> np.ndarray:
     return np.flatnonzero((d == 10) & (par == 0)).astype(np.uint64)
 
 
+def escaped_ends(d: np.ndarray, q: int = 34, e: int = 92):
+    """(record ends, toggles) by the definition's loop (scope "all"), visiting only the bytes that can matter."""
+    pos = np.flatnonzero((d == q) | (d == e) | (d == 10))
+    ends, esc_at, inside, tog = [], -1, 0, 0
+    for p, b in zip(pos.tolist(), d[pos].tolist()):
+        if p == esc_at:
+            continue
+        if b == e:
+            esc_at = p + 1
+        elif b == q:
+            inside ^= 1
+            tog += 1
+        elif not inside:
+            ends.append(p)
+    return np.asarray(ends, np.uint64), tog
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -79,12 +98,21 @@ def main():
     ends = model_ends(block)
     assert int(np.count_nonzero(block == 34)) % 2 == 0 and int(ends[-1]) == len(block) - 1
     exp = np.concatenate([ends + np.uint64(i * len(block)) for i in range(copies)])
+    absent = 1                                                      # an escape byte the quoted block does not hold
+    assert not np.any(block == absent)
+    eblock = synth.csv_escaped(len(block), seed=22)
+    eends, etog = escaped_ends(eblock)
+    assert int(eends[-1]) == len(eblock) - 1 and etog % 2 == 0
+    eexp = np.concatenate([eends + np.uint64(i * len(eblock)) for i in range(copies)])
 
     ctx = get_context(0)
     d = ctx.workspace("quote_rate_in", n + 64, placed=True)
     for i in range(copies):
         ctx.h2d(d.ptr + i * len(block), block)
-    cap = len(exp) + 1024
+    d2 = ctx.workspace("quote_rate_in_escaped", n + 64, placed=True)
+    for i in range(copies):
+        ctx.h2d(d2.ptr + i * len(eblock), eblock)
+    cap = max(len(exp), len(eexp)) + 1024
     nl_cap = copies * int(np.count_nonzero(block == 10)) + 1024
     out = ctx.workspace("quote_rate_out", 8 * max(cap, nl_cap))
     nt = ctx.record_block_tiles(0, n)
@@ -105,6 +133,12 @@ def main():
         ms = ev.stop_ms()
         return ms, ctx.record_ends_result()
 
+    def quote_esc(buf, escape):
+        ev.start()
+        ctx.record_ends_escaped_async(buf.ptr, n, 0, 0, n, 34, 0, escape, 0, "all", out.ptr, True, cap)
+        ms = ev.stop_ms()
+        return ms, ctx.record_ends_escaped_result()
+
     def timed(fn):
         ctx.timing_read()
         fn()
@@ -123,13 +157,21 @@ def main():
 
     ctx.timing(True)
     for _ in range(2):                                              # warm-up of every kernel at this size
-        quote(), quote16(), read(), delim()
-    tq, tb, tr, td = [], [], [], []
+        quote(), quote16(), read(), delim(), quote_esc(d, absent), quote_esc(d2, 92)
+    tq, tb, tr, td, te, te2 = [], [], [], [], [], []
     for _ in range(args.reps):
         tr.append(read())
         td.append(delim())
         ms, res16 = quote16()
         tb.append(ms)
+        ms, rese2 = quote_esc(d2, 92)
+        te2.append(ms)
+        if _ == args.reps - 1:                                      # the escaped buffer's output, before it is reused
+            gote2 = ctx.d2h(np.empty(min(rese2[0], cap), np.uint64), out.ptr)
+        ms, rese = quote_esc(d, absent)
+        te.append(ms)
+        if _ == args.reps - 1:
+            gote = ctx.d2h(np.empty(min(rese[0], cap), np.uint64), out.ptr)
         ms, (n_out, n_quotes, n_newlines) = quote()                 # last: its output is the one verified
         tq.append(ms)
     ctx.timing(False)
@@ -140,6 +182,9 @@ def main():
     got16 = BlockedOffsets(ctx.d2h(np.empty(res16[0], np.uint16), low.ptr), ctx.d2h(np.empty(nt, np.uint64), tab.ptr),
                            0).to_u64()
     ok16 = bool(res16 == (n_out, n_quotes, n_newlines) and np.array_equal(got16, exp))
+
+    oke = bool(rese == (len(exp), n_quotes, n_newlines, n_quotes) and np.array_equal(gote, exp))
+    oke2 = bool(rese2[0] == len(eexp) and rese2[3] == copies * etog and np.array_equal(gote2, eexp))
 
     def rate(ts, nbytes):
         return round(nbytes / (float(np.median(ts)) / 1e3) / GiB, 1)
@@ -157,8 +202,15 @@ def main():
         "record_index_u16b_GiB_per_s": rb, "u16b_ratio_to_stream_read": round(rb / rr, 3),
         "u16b_ms_over_u64_ms": round(float(np.median(tb)) / float(np.median(tq)), 3),
         "index_bytes": {"u64": 8 * int(n_out), "u16b": 2 * int(n_out) + 8 * nt},
-        "newline_index_form": ctx.last_delim_form(), "verified": ok, "verified_u16b": ok16}), flush=True)
-    return 0 if ok and ok16 else 1
+        "escaped_absent_ms": [round(float(np.median(te)), 3), round(min(te), 3), round(max(te), 3)],
+        "escaped_csv_escaped_ms": [round(float(np.median(te2)), 3), round(min(te2), 3), round(max(te2), 3)],
+        "escaped_absent_ms_over_u64_ms": round(float(np.median(te)) / float(np.median(tq)), 3),
+        "escaped_absent_ratio_to_stream_read": round(rate(te, n) / rr, 3),
+        "escaped_csv_escaped_GiB_per_s": rate(te2, n),
+        "escaped_csv_escaped_ratio_to_stream_read": round(rate(te2, n) / rr, 3),
+        "newline_index_form": ctx.last_delim_form(), "verified": ok, "verified_u16b": ok16,
+        "verified_escaped_absent": oke, "verified_escaped": oke2}), flush=True)
+    return 0 if ok and ok16 and oke and oke2 else 1
 
 
 if __name__ == "__main__":
