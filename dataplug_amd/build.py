@@ -1,4 +1,4 @@
-"""Build libdpscan.so and libdpquote.so in-tree for gfx950:  python -m dataplug_amd.build
+"""Build libdpscan.so, libdpquote.so and libdpfai.so in-tree for gfx950:  python -m dataplug_amd.build
 
 The scan library is compiled with -save-temps and the ISA guard (dataplug_amd/isa_guard.py) checks that exact
 device assembly: every kernel, no touched in-flight load destination, no scratch segment.  Only a library that
@@ -25,6 +25,9 @@ OUT_DIAG = os.path.join(HERE, "lib", "libdpscan_diag.so")   # diagnostics: in-ke
 QUOTE_SRC = os.path.join(HERE, "csrc", "dpquote.hip")      # quote-aware CSV record index (include/dpquote.h)
 QUOTE_OUT = os.path.join(HERE, "lib", "libdpquote.so")
 QUOTE_REQUIRED = ("quote_kernel",)                         # the kernels libdpquote.so must contain
+FAI_SRC = os.path.join(HERE, "csrc", "dpfai.hip")          # per-sequence counts of a FASTA .fai (include/dpfai.h)
+FAI_OUT = os.path.join(HERE, "lib", "libdpfai.so")
+FAI_REQUIRED = ("fai_count_kernel", "fai_name_kernel")     # the kernels libdpfai.so must contain
 GZ_SRC = os.path.join(HERE, "csrc", "dpgz.c")
 GZ_PAR_SRC = os.path.join(HERE, "csrc", "dpgz_par.c")     # parallel inflate of one gzip stream
 GZ_OUT = os.path.join(HERE, "lib", "libdpgz.so")            # host-side gzip access-point index (zlib)
@@ -89,6 +92,12 @@ def build_quote(verbose: bool = False) -> str:
     return build(verbose=verbose, out=QUOTE_OUT, src=QUOTE_SRC, required=QUOTE_REQUIRED)
 
 
+def build_fai(verbose: bool = False) -> str:
+    """libdpfai.so: the same hipcc line with -save-temps, the ISA guard on that exact assembly (its own kernel
+    list), installed with its ``.isa.json`` stamp only on "ok"."""
+    return build(verbose=verbose, out=FAI_OUT, src=FAI_SRC, required=FAI_REQUIRED)
+
+
 def build_gz() -> str:
     os.makedirs(os.path.dirname(GZ_OUT), exist_ok=True)
     cc = os.environ.get("CC", "gcc")
@@ -102,3 +111,4 @@ if __name__ == "__main__":
     print(build_gz())
     print(build(verbose="-v" in sys.argv, diag="--diag" in sys.argv))
     print(build_quote(verbose="-v" in sys.argv))
+    print(build_fai(verbose="-v" in sys.argv))

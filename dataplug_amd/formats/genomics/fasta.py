@@ -13,6 +13,11 @@ the attributes then carry ``index_dtype="uint64"`` and ``partition_chunks_strate
   ``chunk_id % n_gpus``.
 * ``merge_fasta_metadata`` — the reference's finalizer (concatenate in chunk order).
 * ``batch_index_fasta`` — the default execution: every chunk in one HIP launch per GPU.
+
+Opt-in ``extra_args={"fai": True}``: a faidx-compatible index (include/dpfai.h) is built on the GPU from the header
+pairs and stored as the samtools text ``NAME\\tLENGTH\\tOFFSET\\tLINEBASES\\tLINEWIDTH\\n`` at ``<key>.fai`` in the meta
+bucket (attributes ``fai_key``, ``num_bases``); ``load_fai``, ``fetch_region`` and ``partition_bases_strategy`` read
+it.  Without it every stored byte and attribute is as before.
 """
 from __future__ import annotations
 
@@ -55,14 +60,35 @@ def _attrs(n: int, dtype) -> dict:
 
 
 def preprocess_fasta(cloud_object: "CloudObject", chunk_data, chunk_id: int, chunk_size: int, num_chunks: int,
-                     index_dtype: str = "uint32"):
-    """Map job (fasta.py:24-63): header pairs of one chunk, scanned on the GPU."""
+                     index_dtype: str = "uint32", fai: bool = False):
+    """Map job (fasta.py:24-63): header pairs of one chunk, scanned on the GPU.  ``fai`` only travels to the
+    finalizer, which builds the .fai from the merged pairs."""
     dtype = _index_dtype(index_dtype)
     data = chunk_data.read()
     chunk_offset = chunk_id * chunk_size
     pairs = scan_objects.fasta_index_chunk(cloud_object, data, chunk_offset, job=chunk_id, u64=dtype == np.uint64)
-    return PreprocessingMetadata(metadata=pairs.astype(dtype, copy=False).tobytes(),
-                                 attributes=None if dtype == np.uint32 else {"index_dtype": index_dtype})
+    attrs = {} if dtype == np.uint32 else {"index_dtype": index_dtype}
+    if fai:
+        attrs["fai"] = True
+    return PreprocessingMetadata(metadata=pairs.astype(dtype, copy=False).tobytes(), attributes=attrs or None)
+
+
+def _with_fai(cloud_object: "CloudObject", meta: PreprocessingMetadata, pairs: np.ndarray) -> PreprocessingMetadata:
+    """Build and store the .fai of ``pairs`` and add its attributes to ``meta``.  On ``FaiFormatError`` the header
+    index is stored as it would be without ``fai`` before the error goes on to the caller."""
+    from ...preprocessing.handler import upload_metadata
+    from ...scan import fai as sfai
+    from ...version import __version__
+    try:
+        names, rows = scan_objects.fai_index_object(cloud_object, pairs)
+    except sfai.FaiFormatError:
+        upload_metadata(cloud_object, meta)
+        raise
+    key = cloud_object.path.key + ".fai"
+    cloud_object.storage.put_object(Body=sfai.fai_text(names, rows), Bucket=cloud_object.meta_path.bucket, Key=key,
+                                    Metadata={"dataplug": __version__})
+    meta.attributes = dict(meta.attributes, fai_key=key, num_bases=int(rows["length"].sum()))
+    return meta
 
 
 def merge_fasta_metadata(cloud_object: "CloudObject", chunk_metadata) -> PreprocessingMetadata:
@@ -73,16 +99,20 @@ def merge_fasta_metadata(cloud_object: "CloudObject", chunk_metadata) -> Preproc
     parts = [np.frombuffer(m.metadata, dtype=dtype) for m in ms]
     num_sequences = int(sum(p.shape[0] / 2 for p in parts))
     idx = np.concatenate(parts) if parts else np.zeros(0, dtype)
-    return PreprocessingMetadata(metadata=idx.tobytes(), attributes=_attrs(num_sequences, dtype))
+    meta = PreprocessingMetadata(metadata=idx.tobytes(), attributes=_attrs(num_sequences, dtype))
+    if any((m.attributes or {}).get("fai") for m in ms):
+        return _with_fai(cloud_object, meta, idx.reshape(-1, 2))
+    return meta
 
 
 def batch_index_fasta(cloud_object: "CloudObject", plan, chunk_size: int, num_chunks: int,
-                      index_dtype: str = "uint32") -> PreprocessingMetadata:
+                      index_dtype: str = "uint32", fai: bool = False) -> PreprocessingMetadata:
     """Map + reduce in one go: the chunk plan scanned on the GPUs (one launch per GPU), already merged."""
     dtype = _index_dtype(index_dtype)
     pairs = scan_objects.fasta_index_object(cloud_object, plan, u64=dtype == np.uint64)
-    return PreprocessingMetadata(metadata=pairs.astype(dtype, copy=False).tobytes(),
+    meta = PreprocessingMetadata(metadata=pairs.astype(dtype, copy=False).tobytes(),
                                  attributes=_attrs(pairs.shape[0], dtype))
+    return _with_fai(cloud_object, meta, pairs) if fai else meta
 
 
 @CloudDataFormat(preprocessing_function=preprocess_fasta, finalizer_function=merge_fasta_metadata,
@@ -210,3 +240,91 @@ def partition_chunks_strategy(cloud_object: "CloudObject", num_chunks: int) -> L
             r1 = a2
         slices.append(FASTASlice(offset=offset, header=header, range_0=r0, range_1=r1))
     return slices
+
+
+# ------------------------------------------------------------------------------------------ .fai (extra_args fai=True)
+def load_fai(cloud_object: "CloudObject"):
+    """(names, rows) of the stored .fai: the names as a list of bytes and ``rows`` a structured array with the
+    fields length, offset, linebases, linewidth.  KeyError when the object was preprocessed without ``fai``."""
+    from ...scan import fai as sfai
+    key = getattr(cloud_object.attributes, "fai_key", None)
+    if key is None:
+        raise KeyError("fai: this object has no .fai; preprocess it with extra_args={'fai': True}")
+    res = cloud_object.storage.get_object(Bucket=cloud_object.meta_path.bucket, Key=key)
+    return sfai.parse_fai(res["Body"].read())
+
+
+def base_to_byte(row, pos: int) -> int:
+    """The object offset of 0-based base ``pos`` (< LENGTH) of a sequence."""
+    lb, lw = int(row["linebases"]), int(row["linewidth"])
+    if lb == 0:
+        return int(row["offset"])
+    return int(row["offset"]) + pos // lb * lw + pos % lb
+
+
+def fetch_region(cloud_object: "CloudObject", name, start: int, end: int) -> bytes:
+    """Bases [start, end) (0-based, half-open) of sequence ``name``, with one ranged GET and the line breaks
+    stripped."""
+    names, rows = load_fai(cloud_object)
+    name = name.encode() if isinstance(name, str) else bytes(name)
+    try:
+        row = rows[names.index(name)]
+    except ValueError:
+        raise KeyError(f"fai: no sequence named {name!r}") from None
+    if not 0 <= start <= end <= int(row["length"]):
+        raise ValueError(f"region [{start}, {end}) outside sequence {name!r} of {int(row['length'])} bases")
+    if start == end:
+        return b""
+    r0, r1 = base_to_byte(row, start), base_to_byte(row, end - 1) + 1
+    res = cloud_object.storage.get_object(Bucket=cloud_object.path.bucket, Key=cloud_object.path.key,
+                                          Range=f"bytes={r0}-{r1 - 1}")
+    return res["Body"].read().replace(b"\n", b"").replace(b"\r", b"")
+
+
+def base_cuts(rows, pairs, size: int, num_chunks: int):
+    """The arithmetic of ``partition_bases_strategy``: [(range_0, range_1, header or None, base offset)], cut at
+    global base positions k * (num_bases // num_chunks) (the last chunk takes the rest)."""
+    lengths = rows["length"].astype(np.int64)
+    cum = np.concatenate([[0], np.cumsum(lengths)])
+    total = int(cum[-1])
+    share = total // num_chunks
+    nonempty = np.flatnonzero(lengths > 0)
+    out = []
+
+    def place(g):
+        """(sequence, base in it) of global base g < total: the sequence that holds it."""
+        i = int(np.searchsorted(cum, g, "right")) - 1
+        return i, g - int(cum[i])
+
+    for k in range(num_chunks):
+        g0 = k * share
+        g1 = total if k == num_chunks - 1 else (k + 1) * share
+        if g1 <= g0 or len(nonempty) == 0:
+            out.append((size, size, None, 0))
+            continue
+        i, pos = place(g0)
+        if pos == 0:
+            r0, header, offset = int(pairs[i][0]), None, 0
+            if k == 0:
+                r0 = 0
+        else:
+            r0, header, offset = base_to_byte(rows[i], pos), (int(pairs[i][0]), int(pairs[i][1])), pos
+        if g1 == total:
+            r1 = size
+        else:
+            j, pos1 = place(g1)
+            r1 = int(pairs[j][0]) if pos1 == 0 else base_to_byte(rows[j], pos1)
+        out.append((r0, r1, header, offset))
+    return out
+
+
+@PartitioningStrategy(dataformat=FASTA)
+def partition_bases_strategy(cloud_object: "CloudObject", num_chunks: int) -> List[FASTASlice]:
+    """``num_chunks`` slices that hold equal shares of the object's bases (``num_bases // num_chunks`` each, the
+    last one the rest), cut at base positions translated to byte offsets through LINEBASES / LINEWIDTH of the
+    stored .fai.  A slice that starts inside a sequence carries that sequence's ``header`` like
+    ``partition_chunks_strategy``'s, and ``offset`` is the 0-based BASE offset of its first base in that sequence."""
+    _, rows = load_fai(cloud_object)
+    pairs = load_index(cloud_object)
+    return [FASTASlice(offset=offset, header=header, range_0=r0, range_1=r1)
+            for r0, r1, header, offset in base_cuts(rows, pairs, cloud_object.size, num_chunks)]

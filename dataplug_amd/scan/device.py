@@ -98,6 +98,7 @@ class ScanContext:
         self._timing_on = False
         self.placements = []                          # per placed buffer: the probe ratios of its candidates
         self._dq = None                               # libdpquote's dq_ctx on this context's stream (record_ends)
+        self._dfai = None                             # libdpfai's dfai_ctx on this context's stream (fai_counts)
 
     # ---------------------------------------------------------------- memory
     def workspace(self, name: str, nbytes: int, placed: bool = False) -> DeviceBuffer:
@@ -586,6 +587,82 @@ class ScanContext:
             return self.d2h(np.empty(n, np.uint16), out.ptr), self.d2h(np.empty(nt, np.uint64), tab.ptr), nq, nn, \
                 ntog
 
+    # ---------------------------------------------------------------- FASTA .fai counts (libdpfai.so)
+    def _fai_ctx(self):
+        """The context's ``dfai_ctx``, created on first use on the context's current stream."""
+        from . import _fai
+        if self._dfai is None:
+            h = ctypes.c_void_p()
+            _fai.check(_fai.load().dfai_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
+            self._dfai = h
+        return _fai.load(), self._dfai
+
+    def fai_geometry(self) -> Tuple[int, int, int]:
+        """(R, the bytes of the range a wave takes at a time; K, the per-wave segment slots; the waves of the grid)
+        of fai_count_kernel (dfai_geometry)."""
+        from . import _fai
+        f, h = self._fai_ctx()
+        r, k, g = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _fai.check(f.dfai_geometry(h, ctypes.byref(r), ctypes.byref(k), ctypes.byref(g)))
+        return int(r.value), int(k.value), int(g.value)
+
+    def fai_counts(self, d_buf: int, buf_len: int, buf_base: int, lo, hi, origin, width=None):
+        """Per-segment counts over device bytes (include/dpfai.h): ``lo``, ``hi``, ``origin`` are uint64 object
+        offsets of n ascending, disjoint segments clipped to the buffer (``origin``: the unclipped body start).
+        Without ``width`` pass 1: (nl, cr, first) uint64 arrays, ``first`` all-ones where the segment holds no
+        '\\n'.  With ``width`` (uint32 per segment) pass 2: (off, lastoff)."""
+        from . import _fai
+        f, h = self._fai_ctx()
+        seg = np.ascontiguousarray(np.stack([np.asarray(a, np.uint64).reshape(-1) for a in (lo, hi, origin)]))
+        n = seg.shape[1]
+        nout = 3 if width is None else 2
+        if n == 0:
+            return tuple(np.zeros(0, np.uint64) for _ in range(nout))
+        ws = self.workspace("fai_seg", 7 * 8 * n + 16)
+        d_seg, d_out, d_w = ws.ptr, ws.ptr + 24 * n, ws.ptr + 48 * n
+        self.h2d(d_seg, seg)
+        p = ctypes.c_void_p
+        if width is None:
+            _fai.check(f.dfai_count_async(h, p(d_buf), buf_len, buf_base, p(d_seg), p(d_seg + 8 * n),
+                                          p(d_seg + 16 * n), n, p(d_out), p(d_out + 8 * n), p(d_out + 16 * n)))
+        else:
+            w = np.ascontiguousarray(np.asarray(width, np.uint32).reshape(-1))
+            if len(w) != n:
+                raise ValueError("width must hold one entry per segment")
+            self.h2d(d_w, w)
+            _fai.check(f.dfai_offgrid_async(h, p(d_buf), buf_len, buf_base, p(d_seg), p(d_seg + 8 * n),
+                                            p(d_seg + 16 * n), p(d_w), n, p(d_out), p(d_out + 8 * n)))
+        out = self.d2h(np.empty((nout, n), np.uint64), d_out)
+        return tuple(out[i] for i in range(nout))
+
+    def fai_names(self, d_buf: int, buf_len: int, buf_base: int, starts, ends):
+        """The names of the headers whose '>' lie at object offsets ``starts`` and which end before ``ends`` (both
+        clipped to the buffer): (lengths uint32, the names packed back to back as uint8) -- the bytes after the '>'
+        up to the first space, tab, '\\r' or '\\n', or up to ``ends``.  Two launches of fai_name_kernel; the
+        exclusive sums between them are made on the host."""
+        from . import _fai
+        f, h = self._fai_ctx()
+        se = np.ascontiguousarray(np.stack([np.asarray(a, np.uint64).reshape(-1) for a in (starts, ends)]))
+        n = se.shape[1]
+        if n == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint8)
+        ws = self.workspace("fai_hdr", 28 * n + 16)
+        d_se, d_off, d_len = ws.ptr, ws.ptr + 16 * n, ws.ptr + 24 * n
+        self.h2d(d_se, se)
+        p = ctypes.c_void_p
+        _fai.check(f.dfai_name_len_async(h, p(d_buf), buf_len, buf_base, p(d_se), p(d_se + 8 * n), n, p(d_len)))
+        lens = self.d2h(np.empty(n, np.uint32), d_len)
+        offs = np.zeros(n, np.uint64)
+        np.cumsum(lens[:-1], dtype=np.uint64, out=offs[1:])
+        total = int(offs[-1]) + int(lens[-1])
+        if total == 0:
+            return lens, np.zeros(0, np.uint8)
+        out = self.workspace("fai_names", total + 16)
+        self.h2d(d_off, offs)
+        _fai.check(f.dfai_name_copy_async(h, p(d_buf), buf_len, buf_base, p(d_se), p(d_len), p(d_off), n,
+                                          p(out.ptr), total))
+        return lens, self.d2h(np.empty(total, np.uint8), out.ptr)
+
     def find_delim(self, d_buf: int, buf_len: int, buf_base: int, start: int, delim: int = 10) -> int:
         """First object offset >= start holding ``delim`` in the buffer, or -1."""
         pos = ctypes.c_int64(-1)
@@ -673,6 +750,10 @@ class ScanContext:
             from . import _quote
             h, self._dq = self._dq, None
             _quote.check(_quote.load().dq_ctx_destroy(h))
+        if self._dfai is not None:
+            from . import _fai
+            h, self._dfai = self._dfai, None
+            _fai.check(_fai.load().dfai_ctx_destroy(h))
         if self.handle:
             for b in list(self._bufs.values()) + list(self._pinned.values()):
                 b.free()

@@ -914,3 +914,108 @@ def record_index_bytes(data, delim: int = 10, every_k: int = 1, emit_add: int = 
     d = ctx.workspace("input", n + 64, placed=True)
     ctx.h2d_async(d.ptr, host.ptr, n)
     return ctx.delim_index(d.ptr, n, 0, 0, n, delim=delim, every_k=every_k, emit_add=emit_add, u64=u64)
+
+
+# ------------------------------------------------------------------------------------------ FASTA .fai
+def _fai_parts(co, bounds, devs, job):
+    """Run ``job(ctx, k, refetch)`` for every part: part k on device entry k mod len(devs), the parts of one entry in
+    order on that entry's persistent worker (the same thread and context in every call).  ``refetch`` tells a job
+    whether its entry holds more than one part, i.e. whether the entry's resident bytes are another part's."""
+    by_dev = {}
+    for k in range(len(bounds)):
+        by_dev.setdefault(k % len(devs), []).append(k)
+
+    def worker(entry):
+        ctx = get_context(devs[entry])
+        for k in by_dev[entry]:
+            job(ctx, k, len(by_dev[entry]) > 1)
+
+    entries = sorted(by_dev)
+    run_on_devices([devs[en] for en in entries], [partial(worker, en) for en in entries])
+
+
+def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: int = 8 << 30, halo: int = _HALO0):
+    """The faidx-compatible index of a FASTA object from its stored header ``pairs`` [(start, end), ...]
+    (include/dpfai.h): ``(names, rows)``, the names as a list of bytes and ``rows`` a ``scan.fai.FAI_DTYPE`` array
+    (length, offset, linebases, linewidth), or ``scan.fai.FaiFormatError`` for the first offending sequence.
+
+    [0, size) is cut with ``line_parts`` and the parts run round-robin on the GPUs.  Per part the bodies are clipped
+    to it and counted on the resident bytes (pass 1 of fai_count_kernel), and the names of the headers whose '>' lies
+    in the part are read with a look-ahead halo like ``FastaGroup``'s (a header line longer than the halo falls back
+    to a ranged GET).  The host merges the parts (counts add, first is a minimum), derives the line widths, and
+    pass 2 runs on the parts again: on the bytes still resident where a GPU entry holds one part, after a second
+    fetch where it holds several."""
+    from . import fai
+    size = int(co.size)
+    p = np.asarray(pairs, np.uint64).reshape(-1, 2)
+    h = len(p)
+    if h == 0:
+        return [], np.zeros(0, fai.FAI_DTYPE)
+    starts, hends = np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+    b, e = fai.bodies(p, size)
+    devs = devices(max_devices, co)
+    bounds = line_parts(0, size, len(devs), part_bytes)
+    nl, cr, off, lastoff = (np.zeros(h, np.uint64) for _ in range(4))
+    first = np.full(h, fai.NONE, np.uint64)
+    name_lens = np.zeros(h, np.uint32)
+    name_bytes = [None] * len(bounds)
+    long_names = {}
+    lock = threading.Lock()
+
+    def clip(k):
+        lo, hi = bounds[k]
+        i0, i1 = int(np.searchsorted(e, lo, "right")), int(np.searchsorted(b, hi, "left"))
+        plo, phi = np.clip(b[i0:i1], lo, hi).astype(np.uint64), np.clip(e[i0:i1], lo, hi).astype(np.uint64)
+        keep = np.flatnonzero(phi > plo)
+        return i0 + keep, plo[keep], phi[keep]
+
+    def resident(ctx, k, fetch):
+        lo, hi = bounds[k]
+        top = min(size, hi + halo)
+        d = ctx.workspace("input", top - lo + 64, placed=True)
+        dp = d.ptr + (lo & 15)
+        if fetch:
+            fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, top, dp)
+        return dp, top
+
+    def pass1(ctx, k, _):
+        lo, hi = bounds[k]
+        dp, top = resident(ctx, k, True)
+        idx, plo, phi = clip(k)
+        r = ctx.fai_counts(dp, top - lo, lo, plo, phi, b[idx])
+        j0, j1 = int(np.searchsorted(starts, lo, "left")), int(np.searchsorted(starts, hi, "left"))
+        cut = np.minimum(hends[j0:j1], np.uint64(top))
+        lens, packed = ctx.fai_names(dp, top - lo, lo, starts[j0:j1], cut)
+        with lock:
+            nl[idx] += r[0]
+            cr[idx] += r[1]
+            first[idx] = np.minimum(first[idx], r[2])
+            name_lens[j0:j1] = lens
+            name_bytes[k] = packed
+            # a name that runs into the end of the fetched bytes before the header line ends: the halo was too short
+            for j in np.flatnonzero((starts[j0:j1] + np.uint64(1) + lens == cut) & (cut < hends[j0:j1])):
+                long_names[j0 + int(j)] = None
+
+    _fai_parts(co, bounds, devs, pass1)
+    names = fai.split_names(name_lens, np.concatenate(name_bytes) if name_bytes else np.zeros(0, np.uint8))
+    for j in long_names:
+        raw = co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key,
+                                    Range=f"bytes={int(starts[j]) + 1}-{int(hends[j]) - 1}")["Body"].read()
+        for stop in (b" ", b"\t", b"\r", b"\n"):
+            raw = raw.split(stop, 1)[0]
+        names[j] = raw
+    width = fai.line_widths(b, e, nl, first)
+    w32 = np.minimum(width, np.uint64(0xFFFFFFFF)).astype(np.uint32)     # (a wider one is an error anyway)
+
+    def pass2(ctx, k, refetch):
+        lo, hi = bounds[k]
+        dp, top = resident(ctx, k, refetch)
+        idx, plo, phi = clip(k)
+        r = ctx.fai_counts(dp, top - lo, lo, plo, phi, b[idx], width=w32[idx])
+        with lock:
+            off[idx] += r[0]
+            lastoff[idx] = np.maximum(lastoff[idx], r[1])
+
+    if (nl > 0).any():
+        _fai_parts(co, bounds, devs, pass2)
+    return names, fai.derive(b, e, nl, cr, first, off, lastoff, names)
