@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from ._lib import DPScanError, DPScanUnavailable, guard_check
+from ._lib import load_guarded, raise_for
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPFAI_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libdpfai.so"))
@@ -46,24 +46,7 @@ def load(path: str = None):
     global _lib
     if path is None and _lib is not None:
         return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise DPScanUnavailable(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; "
-                                f"g.build()'` (hipcc --offload-arch=gfx950)")
-    guard_check(p)
-    try:
-        lib = ctypes.CDLL(p)
-    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
-        raise DPScanUnavailable(f"cannot load {p}: {e}") from e
-    for name, res, args in SIGNATURES:
-        fn = getattr(lib, name, None)
-        if fn is None:
-            raise DPScanUnavailable(f"{p} does not export {name}: rebuild it")
-        fn.restype = res
-        fn.argtypes = args
-    ver = int(lib.dfai_abi_version())
-    if ver != ABI_VERSION:
-        raise DPScanUnavailable(f"{p} has ABI version {ver}, this binding needs {ABI_VERSION}: rebuild it")
+    lib = load_guarded(path or LIB_PATH, SIGNATURES, "dfai_abi_version", ABI_VERSION, exact=True)
     if path is None:
         _lib = lib
     return lib
@@ -75,4 +58,4 @@ def last_error() -> str:
 
 def check(rc: int) -> None:
     if rc != DFAI_OK:
-        raise DPScanError(rc, last_error())
+        raise_for(rc, last_error())

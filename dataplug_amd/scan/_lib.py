@@ -96,34 +96,48 @@ _lib = None
 ABI_VERSION = 2                          # include/dpscan.h DP_ABI_VERSION: the oldest library these signatures fit
 
 
-def load():
-    """Load libdpscan.so once (raises DPScanUnavailable)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise DPScanUnavailable(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; "
+def load_guarded(path: str, signatures, abi_symbol: str, abi_version: int, *, exact: bool,
+                 tolerate_missing: bool = False, abi_note: str = ""):
+    """The one way a library of this package is loaded (raises DPScanUnavailable): the file exists, its ISA-guard
+    stamp passed for exactly this file, it loads, its ``abi_symbol()`` is ``abi_version`` (``exact``) or at least that
+    -- asked before anything else is bound -- and it exports every one of ``signatures``, which are bound.
+    ``tolerate_missing`` waives the version refusal and entry points other than ``abi_symbol`` that are missing."""
+    if not os.path.exists(path):
+        raise DPScanUnavailable(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; "
                                 f"g.build()'` (hipcc --offload-arch=gfx950)")
-    guard_check(LIB_PATH)
+    guard_check(path)
     try:
-        lib = ctypes.CDLL(LIB_PATH)
+        lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
-        raise DPScanUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-    lib.dp_abi_version.restype = ctypes.c_int
-    ver = int(lib.dp_abi_version())
-    if ver < ABI_VERSION and "DPSCAN_LIB" not in os.environ:
-        raise DPScanUnavailable(f"{LIB_PATH} has ABI version {ver}, this binding needs {ABI_VERSION} "
-                                f"(dp_scan_delim_form's argument list changed in 2): rebuild it")
-    for name, res, args in SIGNATURES:
+        raise DPScanUnavailable(f"cannot load {path}: {e}") from e
+    abi = getattr(lib, abi_symbol, None)
+    if abi is None:
+        raise DPScanUnavailable(f"{path} does not export {abi_symbol}: rebuild it")
+    abi.restype = ctypes.c_int
+    ver = int(abi())
+    if (ver != abi_version if exact else ver < abi_version) and not tolerate_missing:
+        raise DPScanUnavailable(f"{path} has ABI version {ver}, this binding needs {abi_version}{abi_note}: "
+                                f"rebuild it")
+    for name, res, args in signatures:
         fn = getattr(lib, name, None)
         if fn is None:
-            if "DPSCAN_LIB" in os.environ:     # an older build loaded for a same-box A/B: it lacks newer entry points
+            if tolerate_missing:
                 continue
-            raise DPScanUnavailable(f"{LIB_PATH} does not export {name}: rebuild it")
+            raise DPScanUnavailable(f"{path} does not export {name}: rebuild it")
         fn.restype = res
         fn.argtypes = args
-    _lib = lib
     return lib
+
+
+def load():
+    """Load libdpscan.so once (raises DPScanUnavailable).  Any library at least as new as the binding will do, and
+    one named by DPSCAN_LIB is an older build loaded for a same-box A/B: it may lack newer entry points."""
+    global _lib
+    if _lib is None:
+        _lib = load_guarded(LIB_PATH, SIGNATURES, "dp_abi_version", ABI_VERSION, exact=False,
+                            tolerate_missing="DPSCAN_LIB" in os.environ,
+                            abi_note=" (dp_scan_delim_form's argument list changed in 2)")
+    return _lib
 
 
 def guard_check(path: str) -> dict:
@@ -144,15 +158,17 @@ def guard_check(path: str) -> dict:
     return rep
 
 
-def check(rc: int) -> None:
-    if rc == DP_OK:
-        return
-    msg = (load().dp_last_error() or b"").decode(errors="replace")
+def raise_for(rc: int, msg: str, extra=()) -> None:
+    """Raise what the non-zero status ``rc`` of any of the three libraries means (they share the codes):
+    OverflowError, DPCapacityError, a library's own ``extra`` ((code, DPScanError subclass) pairs), else DPScanError."""
     if rc == DP_ERR_OVERFLOW:
         raise OverflowError(msg or "Python integer out of bounds for uint32")
-    if rc == DP_ERR_CAPACITY:
-        raise DPCapacityError(rc, msg)
-    raise DPScanError(rc, msg)
+    raise dict(extra).get(rc, DPCapacityError if rc == DP_ERR_CAPACITY else DPScanError)(rc, msg)
+
+
+def check(rc: int) -> None:
+    if rc != DP_OK:
+        raise_for(rc, (load().dp_last_error() or b"").decode(errors="replace"))
 
 
 def alloc_counts():

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from ._lib import DPCapacityError, DPScanError, DPScanUnavailable, guard_check
+from ._lib import DPScanError, load_guarded, raise_for
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPQUOTE_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libdpquote.so"))
@@ -57,24 +57,7 @@ def load(path: str = None):
     global _lib
     if path is None and _lib is not None:
         return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise DPScanUnavailable(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; "
-                                f"g.build()'` (hipcc --offload-arch=gfx950)")
-    guard_check(p)
-    try:
-        lib = ctypes.CDLL(p)
-    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
-        raise DPScanUnavailable(f"cannot load {p}: {e}") from e
-    for name, res, args in SIGNATURES:
-        fn = getattr(lib, name, None)
-        if fn is None:
-            raise DPScanUnavailable(f"{p} does not export {name}: rebuild it")
-        fn.restype = res
-        fn.argtypes = args
-    ver = int(lib.dq_abi_version())
-    if ver != ABI_VERSION:
-        raise DPScanUnavailable(f"{p} has ABI version {ver}, this binding needs {ABI_VERSION}: rebuild it")
+    lib = load_guarded(path or LIB_PATH, SIGNATURES, "dq_abi_version", ABI_VERSION, exact=True)
     if path is None:
         _lib = lib
     return lib
@@ -95,13 +78,5 @@ def last_error() -> str:
 
 
 def check(rc: int) -> None:
-    if rc == DQ_OK:
-        return
-    msg = last_error()
-    if rc == DQ_ERR_OVERFLOW:
-        raise OverflowError(msg or "Python integer out of bounds for uint32")
-    if rc == DQ_ERR_CAPACITY:
-        raise DPCapacityError(rc, msg)
-    if rc == DQ_ERR_ESCAPE_RUN:
-        raise DPEscapeRunError(rc, msg)
-    raise DPScanError(rc, msg)
+    if rc != DQ_OK:
+        raise_for(rc, last_error(), ((DQ_ERR_ESCAPE_RUN, DPEscapeRunError),))

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
+from collections import namedtuple
 from typing import Iterable, Optional, Sequence, Tuple
 
 import numpy as np
@@ -26,6 +27,39 @@ def _host_ptr(data) -> Tuple[int, int, object]:
     else:
         a = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
     return a.ctypes.data, a.nbytes, a
+
+
+def _check_capacity(rc: int, needed: int) -> None:
+    """``check`` for a libdpscan status that may be DP_ERR_CAPACITY: that one raised with the entries ``needed``."""
+    if rc == _lib.DP_ERR_CAPACITY:
+        e = DPCapacityError(rc, f"output capacity below {needed} entries")
+        e.needed = needed
+        raise e
+    check(rc)
+
+
+def _retry_capacity(cap: int, launch):
+    """The result of ``launch(cap)``: launched again, with the capacity the DPCapacityError says is ``needed``, until
+    the output fits (the synchronous forms of every index share this loop)."""
+    while True:
+        try:
+            return launch(cap)
+        except DPCapacityError as e:
+            cap = e.needed
+
+
+# the record index (libdpquote.so): what a launch counts, and what the synchronous ``ScanContext.records`` returns
+RecordCounts = namedtuple("RecordCounts", "n n_quotes n_newlines toggles")
+Records = namedtuple("Records", "ends table n_quotes n_newlines toggles n")
+_RECORD_FORMS = {"count": None, "u32": np.uint32, "u64": np.uint64, "u16b": np.uint16}
+
+
+def _record_form(form: str, escape: Optional[int], scope: str):
+    """(output dtype, escape flags) of a record launch; ValueError for an unknown form or, with an escape, scope."""
+    from ._quote import escape_flags
+    if form not in _RECORD_FORMS:
+        raise ValueError(f"record form must be one of {tuple(_RECORD_FORMS)}, not {form!r}")
+    return _RECORD_FORMS[form], 0 if escape is None else escape_flags(scope)
 
 
 class DeviceBuffer:
@@ -97,7 +131,7 @@ class ScanContext:
         self._get_pool = None
         self._timing_on = False
         self.placements = []                          # per placed buffer: the probe ratios of its candidates
-        self._dq = None                               # libdpquote's dq_ctx on this context's stream (record_ends)
+        self._dq = None                               # libdpquote's dq_ctx on this context's stream (records)
         self._dfai = None                             # libdpfai's dfai_ctx on this context's stream (fai_counts)
 
     # ---------------------------------------------------------------- memory
@@ -244,18 +278,15 @@ class ScanContext:
         pending = np.full(nch, -1, np.int64)
         cend = np.zeros(nch, np.uint64)
         n = ctypes.c_uint64(0)
-        while True:
+
+        def launch(cap):
             out = self.workspace("out", 2 * cap * np.dtype(dtype).itemsize + 16)
             rc = self.lib.dp_fasta_index(self.handle, ctypes.c_void_p(d_buf), buf_len, buf_base, obj_size,
                                          ch.ctypes.data_as(_U64P), nch, ctypes.c_void_p(out.ptr), int(u64), cap,
                                          ctypes.byref(n), pending.ctypes.data_as(_I64P), cend.ctypes.data_as(_U64P))
-            if rc == _lib.DP_ERR_CAPACITY:
-                cap = int(n.value)
-                continue
-            check(rc)
-            break
-        pairs = self.d2h(np.empty((int(n.value), 2), dtype), out.ptr)
-        return pairs, pending, cend
+            _check_capacity(rc, int(n.value))
+            return self.d2h(np.empty((int(n.value), 2), dtype), out.ptr)
+        return _retry_capacity(cap, launch), pending, cend
 
     def fasta_index_async(self, d_buf, buf_len, buf_base, obj_size, chunks_u64: np.ndarray, d_out: int,
                           u64: bool, cap: int) -> None:
@@ -282,17 +313,15 @@ class ScanContext:
             cap = (end - begin) // (16 * every_k) + 1024
         n = ctypes.c_uint64(0)
         nd = ctypes.c_uint64(0)
-        while True:
+
+        def launch(cap):
             out = self.workspace("out", cap * np.dtype(dtype).itemsize + 16)
             rc = self.lib.dp_delim_index(self.handle, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end,
                                          int(delim), int(every_k), int(emit_add), ctypes.c_void_p(out.ptr),
                                          int(u64), cap, ctypes.byref(n), ctypes.byref(nd))
-            if rc == _lib.DP_ERR_CAPACITY:
-                cap = int(n.value)
-                continue
-            check(rc)
-            break
-        return self.d2h(np.empty(int(n.value), dtype), out.ptr), int(nd.value)
+            _check_capacity(rc, int(n.value))
+            return self.d2h(np.empty(int(n.value), dtype), out.ptr), int(nd.value)
+        return _retry_capacity(cap, launch)
 
     def delim_index_async(self, d_buf, buf_len, buf_base, begin, end, delim, every_k, emit_add, d_out, u64, cap):
         check(self.lib.dp_delim_index_async(self.handle, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end,
@@ -320,11 +349,7 @@ class ScanContext:
         nd = ctypes.c_uint64(0)
         ends = np.zeros(nranges, np.uint64)
         rc = self.lib.dp_delim_ranges_result(self.handle, ctypes.byref(n), ctypes.byref(nd), ends.ctypes.data_as(_U64P))
-        if rc == _lib.DP_ERR_CAPACITY:
-            e = DPCapacityError(rc, f"output capacity below {int(n.value)} entries")
-            e.needed = int(n.value)
-            raise e
-        check(rc)
+        _check_capacity(rc, int(n.value))
         return int(n.value), int(nd.value), ends
 
     @staticmethod
@@ -385,21 +410,19 @@ class ScanContext:
         dtype = {0: np.uint32, 1: np.uint64, 2: np.uint32, 3: np.uint16, 4: np.uint8}[out_mode]
         if cap is None:
             cap = span // (16 * every_k) + 1024
-        while True:
+
+        def launch(cap):
             out = self.workspace("out", self.out_bytes(cap, out_mode, rg))
             self.delim_ranges_async(d_buf, buf_len, buf_base, rg, delim, every_k, emit_add, carry, out.ptr,
                                     out_mode, cap)
-            try:
-                n, nd, ends = self.delim_ranges_result(len(rg) // 2)
-            except DPCapacityError as e:
-                cap = e.needed
-                continue
+            n, nd, ends = self.delim_ranges_result(len(rg) // 2)
             vals = self.d2h(np.empty(n, dtype), out.ptr)
             if out_mode == 3:
                 return vals, nd, ends, self.block_table(out.ptr, cap, rg)
             if out_mode == 4:
                 return vals, nd, ends, self.block_table(out.ptr, cap, rg, 4), self.sub_table(out.ptr, cap, rg)
             return vals, nd, ends
+        return _retry_capacity(cap, launch)
 
     # ---------------------------------------------------------------- quote-aware record ends (libdpquote.so)
     def _quote_ctx(self):
@@ -420,172 +443,79 @@ class ScanContext:
         _quote.check(q.dq_geometry(h, ctypes.byref(g), ctypes.byref(t)))
         return int(t.value), int(g.value)
 
-    def record_ends_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int,
-                          carry: int, d_out: int, u64: bool, cap: int) -> None:
-        from . import _quote
-        q, h = self._quote_ctx()
-        _quote.check(q.dq_records_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote),
-                                        int(carry), ctypes.c_void_p(d_out or 0), int(u64), int(cap)))
-
-    def record_ends_result(self) -> Tuple[int, int, int]:
-        """(record ends, quote bytes, newlines) of the launch in flight; DPCapacityError carries ``needed``."""
-        from . import _quote
-        q, h = self._quote_ctx()
-        n, nq, nn = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        rc = q.dq_records_result(h, ctypes.byref(n), ctypes.byref(nq), ctypes.byref(nn))
-        if rc == _quote.DQ_ERR_CAPACITY:
-            e = DPCapacityError(rc, _quote.last_error())
-            e.needed, e.n_quotes, e.n_newlines = int(n.value), int(nq.value), int(nn.value)
-            raise e
-        _quote.check(rc)
-        return int(n.value), int(nq.value), int(nn.value)
-
-    def record_counts(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
-                      carry: int = 0) -> Tuple[int, int, int]:
-        """The count-only launch: (record ends, quote bytes, newlines) of object bytes [begin, end)."""
-        self.record_ends_async(d_buf, buf_len, buf_base, begin, end, quote, carry, 0, True, 0)
-        return self.record_ends_result()
-
-    def record_ends(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
-                    carry: int = 0, u64: bool = True, cap: Optional[int] = None):
-        """Sorted object offsets of the '\\n' that end a CSV record in object bytes [begin, end): those with an even
-        number of ``quote`` bytes (plus ``carry``) before them (dq_records_async; include/dpquote.h).
-
-        Returns (offsets uint64|uint32, quote bytes seen, newlines seen)."""
-        dtype = np.uint64 if u64 else np.uint32
-        if cap is None:
-            cap = (end - begin) // 16 + 1024
-        while True:
-            out = self.workspace("out", cap * np.dtype(dtype).itemsize + 16)
-            self.record_ends_async(d_buf, buf_len, buf_base, begin, end, quote, carry, out.ptr, u64, cap)
-            try:
-                n, nq, nn = self.record_ends_result()
-            except DPCapacityError as e:
-                cap = e.needed
-                continue
-            return self.d2h(np.empty(n, dtype), out.ptr), nq, nn
-
-    def record_ends_blocked_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int,
-                                  carry: int, d_low: int, cap: int, d_table: int, table_cap: int) -> None:
-        """dq_records_blocked_async: uint16 low words at ``d_low``, the 64 KiB block table at ``d_table``; collected
-        by ``record_ends_result``.  The device address of ``begin`` must be congruent to ``begin`` mod 16."""
-        from . import _quote
-        q, h = self._quote_ctx()
-        _quote.check(q.dq_records_blocked_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote),
-                                                int(carry), ctypes.c_void_p(d_low or 0), int(cap),
-                                                ctypes.c_void_p(d_table or 0), int(table_cap)))
-
     @staticmethod
     def record_block_tiles(begin: int, end: int) -> int:
         """Entries of the block table of object bytes [begin, end): the 64 KiB blocks that hold one of them."""
         return ((end - 1) >> 16) - (begin >> 16) + 1 if end > begin else 0
 
-    def record_ends_blocked(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
-                            carry: int = 0, cap: Optional[int] = None):
-        """``record_ends`` in the blocked form u16b, written by the kernel: the low 16 bits of every record end's
-        object offset and ``table[j]`` = the record ends before object offset ``((begin >> 16) + j) << 16``
-        (``scan.objects.BlockedOffsets(low, table, begin >> 16)`` decodes them).
+    def records_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, *, quote: int = 34,
+                      carry: int = 0, escape: Optional[int] = None, esc_carry: int = 0, scope: str = "all", form: str,
+                      d_out: int = 0, cap: int = 0, d_table: int = 0, table_cap: int = 0) -> None:
+        """One launch of the record-end kernel over object bytes [begin, end) (include/dpquote.h), collected by
+        ``records_result``: the only place that picks among the dq_records_*_async entry points.  ``form`` "u32" /
+        "u64": offsets at ``d_out``; "u16b": uint16 low words at ``d_out`` and the 64 KiB block table at ``d_table``
+        (the device address of ``begin`` must be congruent to ``begin`` mod 16); "count": no output.  ``escape``: the
+        byte after an unescaped escape byte is literal (``esc_carry``: the byte at ``begin`` is escaped; ``scope``
+        "all" or "quoted"), None: the plain launch."""
+        from . import _quote
+        _, flags = _record_form(form, escape, scope)
+        esc = () if escape is None else (int(escape), int(esc_carry), flags)
+        q, h = self._quote_ctx()
+        if form == "u16b":
+            fn = q.dq_records_blocked_async if escape is None else q.dq_records_esc_blocked_async
+            out = (ctypes.c_void_p(d_out or 0), int(cap), ctypes.c_void_p(d_table or 0), int(table_cap))
+        else:
+            fn = q.dq_records_async if escape is None else q.dq_records_esc_async
+            if form == "count":
+                d_out = cap = 0
+            out = (ctypes.c_void_p(d_out or 0), int(form != "u32"), int(cap))
+        _quote.check(fn(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote), int(carry), *esc, *out))
 
-        Returns (low uint16, table uint64, quote bytes seen, newlines seen)."""
-        if cap is None:
-            cap = (end - begin) // 16 + 1024
-        nt = self.record_block_tiles(begin, end)
-        while True:
-            out = self.workspace("out", cap * 2 + 16)
-            tab = self.workspace("record_blocks", nt * 8 + 16)
-            self.record_ends_blocked_async(d_buf, buf_len, buf_base, begin, end, quote, carry, out.ptr, cap,
-                                           tab.ptr, nt)
-            try:
-                n, nq, nn = self.record_ends_result()
-            except DPCapacityError as e:
-                cap = e.needed
-                continue
-            return self.d2h(np.empty(n, np.uint16), out.ptr), self.d2h(np.empty(nt, np.uint64), tab.ptr), nq, nn
-
-    # ---------------------------------------------------------------- ... with an escape byte (dq_records_esc_*)
-    def record_ends_escaped_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int,
-                                  carry: int, escape: int, esc_carry: int, scope: str, d_out: int, u64: bool,
-                                  cap: int) -> None:
+    def records_result(self) -> RecordCounts:
+        """(record ends, quote bytes, newlines, toggles) of the launch in flight: ``toggles`` are the quote bytes that
+        are not escaped (all of them after a plain launch).  DPCapacityError carries ``needed``, ``n_quotes``,
+        ``n_newlines`` and ``n_toggles``; a run of escape bytes beyond DQ_ESCAPE_RUN_MAX raises
+        ``_quote.DPEscapeRunError``."""
         from . import _quote
         q, h = self._quote_ctx()
-        _quote.check(q.dq_records_esc_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end, int(quote),
-                                            int(carry), int(escape), int(esc_carry), _quote.escape_flags(scope),
-                                            ctypes.c_void_p(d_out or 0), int(u64), int(cap)))
-
-    def record_ends_escaped_result(self) -> Tuple[int, int, int, int]:
-        """(record ends, quote bytes, newlines, toggles) of the launch in flight: ``toggles`` are the quote bytes
-        that are not escaped; DPCapacityError carries ``needed``, a run of escape bytes beyond DQ_ESCAPE_RUN_MAX
-        raises ``_quote.DPEscapeRunError``."""
-        from . import _quote
-        q, h = self._quote_ctx()
-        n, nq, nn, nt = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        rc = q.dq_records_esc_result(h, ctypes.byref(n), ctypes.byref(nq), ctypes.byref(nn), ctypes.byref(nt))
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        rc = q.dq_records_esc_result(h, *(ctypes.byref(x) for x in v))
+        res = RecordCounts(*(int(x.value) for x in v))
         if rc == _quote.DQ_ERR_CAPACITY:
             e = DPCapacityError(rc, _quote.last_error())
-            e.needed, e.n_quotes, e.n_newlines, e.n_toggles = int(n.value), int(nq.value), int(nn.value), \
-                int(nt.value)
+            e.needed, e.n_quotes, e.n_newlines, e.n_toggles = res
             raise e
         _quote.check(rc)
-        return int(n.value), int(nq.value), int(nn.value), int(nt.value)
+        return res
 
-    def record_counts_escaped(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
-                              carry: int = 0, escape: int = 92, esc_carry: int = 0,
-                              scope: str = "all") -> Tuple[int, int, int, int]:
-        """The count-only launch with an escape byte: (record ends, quote bytes, newlines, toggles)."""
-        self.record_ends_escaped_async(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry, scope,
-                                       0, True, 0)
-        return self.record_ends_escaped_result()
+    def records(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, *, quote: int = 34,
+                carry: int = 0, escape: Optional[int] = None, esc_carry: int = 0, scope: str = "all",
+                form: str = "u64", cap: Optional[int] = None) -> Records:
+        """Sorted object offsets of the '\\n' that end a CSV record in object bytes [begin, end): those with an even
+        number of ``quote`` bytes (plus ``carry``) before them, escaped quotes not counted (``records_async``).
 
-    def record_ends_escaped(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, quote: int = 34,
-                            carry: int = 0, escape: int = 92, esc_carry: int = 0, scope: str = "all",
-                            u64: bool = True, cap: Optional[int] = None):
-        """``record_ends`` for the dialect that escapes a quote inside a field with ``escape`` (include/dpquote.h:
-        a byte after an unescaped escape byte is literal; ``esc_carry`` = the byte at ``begin`` is escaped; ``scope``
-        "all" or "quoted").  Returns (offsets uint64|uint32, quote bytes seen, newlines seen, toggles)."""
-        dtype = np.uint64 if u64 else np.uint32
-        if cap is None:
-            cap = (end - begin) // 16 + 1024
-        while True:
-            out = self.workspace("out", cap * np.dtype(dtype).itemsize + 16)
-            self.record_ends_escaped_async(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry,
-                                           scope, out.ptr, u64, cap)
-            try:
-                n, nq, nn, nt = self.record_ends_escaped_result()
-            except DPCapacityError as e:
-                cap = e.needed
-                continue
-            return self.d2h(np.empty(n, dtype), out.ptr), nq, nn, nt
-
-    def record_ends_blocked_escaped_async(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int,
-                                          quote: int, carry: int, escape: int, esc_carry: int, scope: str,
-                                          d_low: int, cap: int, d_table: int, table_cap: int) -> None:
-        from . import _quote
-        q, h = self._quote_ctx()
-        _quote.check(q.dq_records_esc_blocked_async(h, ctypes.c_void_p(d_buf), buf_len, buf_base, begin, end,
-                                                    int(quote), int(carry), int(escape), int(esc_carry),
-                                                    _quote.escape_flags(scope), ctypes.c_void_p(d_low or 0),
-                                                    int(cap), ctypes.c_void_p(d_table or 0), int(table_cap)))
-
-    def record_ends_blocked_escaped(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int,
-                                    quote: int = 34, carry: int = 0, escape: int = 92, esc_carry: int = 0,
-                                    scope: str = "all", cap: Optional[int] = None):
-        """``record_ends_blocked`` with an escape byte: (low uint16, table uint64, quote bytes seen, newlines seen,
-        toggles)."""
+        ``ends``: uint64 | uint32 offsets; for "u16b" the low 16 bits of each, with ``table[j]`` = the record ends
+        before object offset ``((begin >> 16) + j) << 16`` (``scan.objects.BlockedOffsets(ends, table, begin >> 16)``
+        decodes them); for "count" None, one launch without output.  ``n``: the record ends."""
+        dtype, _ = _record_form(form, escape, scope)
+        kw = dict(quote=quote, carry=carry, escape=escape, esc_carry=esc_carry, scope=scope, form=form)
+        if form == "count":
+            self.records_async(d_buf, buf_len, buf_base, begin, end, **kw)
+            r = self.records_result()
+            return Records(None, None, *r[1:], r.n)
         if cap is None:
             cap = (end - begin) // 16 + 1024
         nt = self.record_block_tiles(begin, end)
-        while True:
-            out = self.workspace("out", cap * 2 + 16)
-            tab = self.workspace("record_blocks", nt * 8 + 16)
-            self.record_ends_blocked_escaped_async(d_buf, buf_len, buf_base, begin, end, quote, carry, escape,
-                                                   esc_carry, scope, out.ptr, cap, tab.ptr, nt)
-            try:
-                n, nq, nn, ntog = self.record_ends_escaped_result()
-            except DPCapacityError as e:
-                cap = e.needed
-                continue
-            return self.d2h(np.empty(n, np.uint16), out.ptr), self.d2h(np.empty(nt, np.uint64), tab.ptr), nq, nn, \
-                ntog
+
+        def launch(cap):
+            out = self.workspace("out", cap * np.dtype(dtype).itemsize + 16)
+            tab = self.workspace("record_blocks", nt * 8 + 16) if form == "u16b" else None
+            self.records_async(d_buf, buf_len, buf_base, begin, end, d_out=out.ptr, cap=cap,
+                               d_table=tab.ptr if tab else 0, table_cap=nt if tab else 0, **kw)
+            r = self.records_result()
+            return Records(self.d2h(np.empty(r.n, dtype), out.ptr),
+                           self.d2h(np.empty(nt, np.uint64), tab.ptr) if tab else None, *r[1:], r.n)
+        return _retry_capacity(cap, launch)
 
     # ---------------------------------------------------------------- FASTA .fai counts (libdpfai.so)
     def _fai_ctx(self):

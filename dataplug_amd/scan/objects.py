@@ -679,12 +679,10 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
         d = ctx.workspace("input", n + 64, placed=True)
         dp = d.ptr + (lo & 15)
         fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
-        if escape is None:
-            n_rec, quotes[k], _ = ctx.record_counts(dp, n, lo, lo, hi, quote=quote, carry=0)
-        else:
-            ec = escape_carry_at(co, begin, lo, escape) if k else 0
-            n_rec, _, _, quotes[k] = ctx.record_counts_escaped(dp, n, lo, lo, hi, quote=quote, carry=0, escape=escape,
-                                                               esc_carry=ec, scope=escape_scope)
+        ec = escape_carry_at(co, begin, lo, escape) if k and escape is not None else 0
+        esc = dict(escape=escape, esc_carry=ec, scope=escape_scope)
+        counts = ctx.records(dp, n, lo, lo, hi, quote=quote, carry=0, form="count", **esc)
+        n_rec, quotes[k] = counts.n, counts.toggles      # a plain launch toggles at every quote byte
         counted[k].set()
         for j in range(k):                               # parts before this one: on this worker done, on others
             while not counted[j].wait(0.05):             # at least counted before they wait for anything
@@ -693,17 +691,9 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
         carry = sum(quotes[:k]) & 1
         # the count under carry 0 bounds nothing under carry 1: size the output by the newlines only on a retry
         cap = max(n_rec, 1) if carry == 0 else None
-        if escape is not None:
-            if fmt == "u16b":
-                out[k] = ctx.record_ends_blocked_escaped(dp, n, lo, lo, hi, quote=quote, carry=carry, escape=escape,
-                                                         esc_carry=ec, scope=escape_scope, cap=cap)[:2]
-            else:
-                out[k] = ctx.record_ends_escaped(dp, n, lo, lo, hi, quote=quote, carry=carry, escape=escape,
-                                                 esc_carry=ec, scope=escape_scope, u64=True, cap=cap)[0]
-        elif fmt == "u16b":                              # dp is congruent to lo mod 16: the blocked form's grid
-            out[k] = ctx.record_ends_blocked(dp, n, lo, lo, hi, quote=quote, carry=carry, cap=cap)[:2]
-        else:
-            out[k] = ctx.record_ends(dp, n, lo, lo, hi, quote=quote, carry=carry, u64=True, cap=cap)[0]
+        # dp is congruent to lo mod 16: the blocked form's grid
+        r = ctx.records(dp, n, lo, lo, hi, quote=quote, carry=carry, form=fmt, cap=cap, **esc)
+        out[k] = (r.ends, r.table) if fmt == "u16b" else r.ends
 
     by_dev = {}
     for k in range(len(bounds)):

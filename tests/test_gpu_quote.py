@@ -1,4 +1,4 @@
-"""libdpquote.so's record-end kernel through ScanContext.record_ends, bit-exact against the numpy model
+"""libdpquote.so's record-end kernel through ScanContext.records, bit-exact against the numpy model
 (tests/_quote_model.py): every length around the chunk / tile edges, contents that put quotes and newlines on those
 edges, both incoming states, unaligned ranges inside larger buffers, the output modes, capacity, and context reuse.
 With T, G = tile bytes, grid: the largest case hands more than one tile to a workgroup (a look-back deeper than one).
@@ -15,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+import _escape_cases as C
+from _escape_loop import blocked
 from _quote_cases import every_value_every_position, one_lane_16
 from _quote_model import record_ends
 from dataplug_amd.scan import DPCapacityError, DPScanError, ScanContext
@@ -38,13 +40,13 @@ def geo(ctx):
 
 def _run(ctx, buf: np.ndarray, lo: int, hi: int, buf_base: int = 0, carry: int = 0, u64: bool = True, mis: int = 0,
          cap=None, quote: int = 34):
-    """record_ends of buffer bytes [lo, hi) -- object bytes [buf_base + lo, buf_base + hi) -- with the buffer placed
+    """records of buffer bytes [lo, hi) -- object bytes [buf_base + lo, buf_base + hi) -- with the buffer placed
     ``mis`` bytes past a 16-byte boundary; checked against the model."""
     d = ctx.workspace("quote_in", len(buf) + 64)
     if len(buf):
         ctx.h2d(d.ptr + mis, buf)
-    got, nq, nn = ctx.record_ends(d.ptr + mis, len(buf), buf_base, buf_base + lo, buf_base + hi, quote=quote,
-                                  carry=carry, u64=u64, cap=cap)
+    got, _, nq, nn, _, _ = ctx.records(d.ptr + mis, len(buf), buf_base, buf_base + lo, buf_base + hi, quote=quote,
+                                       carry=carry, form="u64" if u64 else "u32", cap=cap)
     exp, eq, en = record_ends(buf[lo:hi], base=buf_base + lo, quote=quote, carry=carry)
     assert got.dtype == (np.uint64 if u64 else np.uint32)
     assert (nq, nn) == (eq, en)
@@ -138,21 +140,22 @@ def test_capacity_and_count_only(ctx, geo):
     assert len(exp) > 1000
     d = ctx.workspace("quote_in", len(buf) + 64)
     ctx.h2d(d.ptr, buf)
-    assert ctx.record_counts(d.ptr, len(buf), 50, 50, 50 + len(buf)) == (len(exp), eq, en)
-    assert ctx.record_counts(d.ptr, len(buf), 50, 50, 50 + len(buf), carry=1)[0] == \
+    counts = ctx.records(d.ptr, len(buf), 50, 50, 50 + len(buf), form="count")
+    assert (counts.n, counts.n_quotes, counts.n_newlines) == (len(exp), eq, en)
+    assert ctx.records(d.ptr, len(buf), 50, 50, 50 + len(buf), carry=1, form="count").n == \
         len(record_ends(buf, base=50, carry=1)[0])
     cap = 777
     canary = np.full(len(exp) + 64, 0xEEEEEEEEEEEEEEEE, np.uint64)
     out = ctx.workspace("quote_canary", canary.nbytes)
     ctx.h2d(out.ptr, canary)
-    ctx.record_ends_async(d.ptr, len(buf), 50, 50, 50 + len(buf), 34, 0, out.ptr, True, cap)
+    ctx.records_async(d.ptr, len(buf), 50, 50, 50 + len(buf), quote=34, carry=0, form="u64", d_out=out.ptr, cap=cap)
     with pytest.raises(DPCapacityError) as ei:
-        ctx.record_ends_result()
+        ctx.records_result()
     assert ei.value.needed == len(exp) and (ei.value.n_quotes, ei.value.n_newlines) == (eq, en)
     back = ctx.d2h(np.empty_like(canary), out.ptr)
     assert np.array_equal(back[:cap], exp[:cap])
     assert np.array_equal(back[cap:], canary[cap:]), "written at or beyond cap"
-    got, _, _ = ctx.record_ends(d.ptr, len(buf), 50, 50, 50 + len(buf), cap=1)   # the wrapper retries with the count
+    got = ctx.records(d.ptr, len(buf), 50, 50, 50 + len(buf), cap=1).ends        # the wrapper retries with the count
     assert np.array_equal(got, exp)
 
 
@@ -160,12 +163,12 @@ def test_bad_arguments_are_refused(ctx):
     d = ctx.workspace("quote_in", 4096)
     for kw in ({"quote": 10}, {"quote": 300}, {"carry": 2}):
         with pytest.raises(DPScanError):
-            ctx.record_ends(d.ptr, 100, 0, 0, 100, **kw)
+            ctx.records(d.ptr, 100, 0, 0, 100, **kw)
     with pytest.raises(DPScanError):
-        ctx.record_ends(d.ptr, 100, 10, 5, 50)                      # begins before the buffer
+        ctx.records(d.ptr, 100, 10, 5, 50)                          # begins before the buffer
     with pytest.raises(DPScanError):
-        ctx.record_ends(d.ptr, 100, 10, 20, 111)                    # ends past it
-    assert len(ctx.record_ends(d.ptr, 100, 10, 60, 60)[0]) == 0     # empty range
+        ctx.records(d.ptr, 100, 10, 20, 111)                        # ends past it
+    assert len(ctx.records(d.ptr, 100, 10, 60, 60).ends) == 0       # empty range
 
 
 def test_reuse_of_one_context_and_two_contexts(ctx, geo):
@@ -185,6 +188,51 @@ def test_reuse_of_one_context_and_two_contexts(ctx, geo):
                               record_ends(small[2:], base=2, carry=1)[0])
     finally:
         other.close()
+
+
+# ------------------------------------------------------------------------------------------ the one launch path
+@pytest.fixture(scope="module")
+def three_tiles(ctx, geo):
+    """3 tiles + 17 bytes of quotes, escape bytes and newlines as object bytes [5, ..) at a device address 5 past a
+    16-byte boundary: the smallest input with a tile boundary, a look-back and a ragged tail; \\" across both inner
+    tile edges."""
+    t, _ = geo
+    d = C.random_five(3 * t + 17, 31)
+    for edge in (t - 5, 2 * t - 5):                      # the buffer offsets of both inner tile edges, in every form
+        d[edge - 2:edge] = (ord("a"), C.E)
+        C.after_run(d, edge)
+    c = C.case(d, begin=5, base=5, carry=1, name="three_tiles")
+    dev = ctx.workspace("quote_records_in", len(d) + 64)
+    ctx.h2d(dev.ptr + 5, d)
+    plain = record_ends(d, base=5, carry=1)
+    want = {None: plain + (plain[1],), C.E: C.expect(c)}  # a plain launch toggles at every quote byte
+    assert want[C.E][3] < want[C.E][1] and not np.array_equal(want[C.E][0], plain[0])
+    assert min(len(want[None][0]), len(want[C.E][0])) > 1000
+    return c, dev.ptr + 5, want
+
+
+@pytest.mark.parametrize("escape", [None, C.E])
+@pytest.mark.parametrize("form", ["count", "u32", "u64", "u16b"])
+def test_records_equals_the_definition_in_every_form(ctx, three_tiles, form, escape):
+    c, addr, want = three_tiles
+    d, begin, end = c["buf"], c["begin"], c["end"]
+    ends, nq, nn, tog = want[escape]
+    r = ctx.records(addr, len(d), c["base"], begin, end, carry=c["carry"], escape=escape, form=form)
+    assert (r.n, r.n_quotes, r.n_newlines, r.toggles) == (len(ends), nq, nn, tog)
+    if escape is None:
+        assert r.toggles == r.n_quotes
+    if form == "count":
+        assert r.ends is None and r.table is None
+    elif form == "u16b":
+        low, table = blocked(ends, begin, end)
+        assert r.ends.dtype == np.uint16 and r.table.dtype == np.uint64 and len(table) == 4
+        assert np.array_equal(r.ends, low) and np.array_equal(r.table, table)
+    else:
+        assert r.ends.dtype == (np.uint64 if form == "u64" else np.uint32) and r.table is None
+        assert np.array_equal(r.ends.astype(np.uint64), ends)
+    if form == "u64":                                    # started too small: one relaunch, the same offsets
+        again = ctx.records(addr, len(d), c["base"], begin, end, carry=c["carry"], escape=escape, cap=1)
+        assert np.array_equal(again.ends, r.ends) and again[2:] == r[2:]
 
 
 # ------------------------------------------------------------------------------------------ the lane-exact model
@@ -239,9 +287,10 @@ def test_kernel_equals_lane_model(ctx, geo):
         canary = np.full(n_out + 64, 0xEEEEEEEE, off.dtype)
         out = ctx.workspace("quote_canary", canary.nbytes)
         ctx.h2d(out.ptr, canary)
-        ctx.record_ends_async(d.ptr + 11, len(buf), 50, 50, 50 + len(buf), 34, 1, out.ptr, u64, cap)
+        ctx.records_async(d.ptr + 11, len(buf), 50, 50, 50 + len(buf), quote=34, carry=1,
+                          form="u64" if u64 else "u32", d_out=out.ptr, cap=cap)
         with pytest.raises(DPCapacityError) as ei:
-            ctx.record_ends_result()
+            ctx.records_result()
         assert (ei.value.needed, ei.value.n_quotes, ei.value.n_newlines) == (n_out, nq, nn)
         back = ctx.d2h(np.empty_like(canary), out.ptr)
         assert np.array_equal(back[:cap], off) and np.array_equal(back[cap:], canary[cap:])

@@ -1,5 +1,5 @@
 """The blocked form u16b of libdpquote.so's record-end kernel (quote_kernel<2>) on the GPU, through
-ScanContext.record_ends_blocked: the uint16 low words and the 64 KiB block table bit-equal to the lane-exact model
+ScanContext.records(form="u16b"): the uint16 low words and the 64 KiB block table bit-equal to the lane-exact model
 (tools/emulate_quote.py) and, decoded by BlockedOffsets, equal to the definition (tests/_quote_model.py).  With
 T = 64 KiB and b0 = begin & 0xFFFF: lengths around the chunk and tile edges, first tiles entered up to 65535 bytes in,
 both incoming states, more tiles than workgroups, tiles without a record end, object offsets above 2^32, canaries
@@ -59,10 +59,11 @@ def place(ctx, buf, lo, begin, name="quote_in"):
 
 
 def run_blocked(ctx, buf, lo, hi, begin, carry=0, cap=None, quote=34):
-    """record_ends_blocked of buf[lo:hi] as object bytes [begin, begin + hi - lo), checked against the definition."""
+    """records(form="u16b") of buf[lo:hi] as object bytes [begin, begin + hi - lo), checked against the definition."""
     addr, buf_base = place(ctx, buf, lo, begin)
     end = begin + hi - lo
-    low, table, nq, nn = ctx.record_ends_blocked(addr, len(buf), buf_base, begin, end, quote=quote, carry=carry, cap=cap)
+    low, table, nq, nn, _, _ = ctx.records(addr, len(buf), buf_base, begin, end, quote=quote, carry=carry, form="u16b",
+                                           cap=cap)
     exp, eq, en = record_ends(buf[lo:hi], base=begin, quote=quote, carry=carry)
     assert low.dtype == np.uint16 and table.dtype == np.uint64 and (nq, nn) == (eq, en)
     assert len(table) == tiles_of(begin, end) and np.array_equal(table, table_of(exp, begin, end))
@@ -152,13 +153,14 @@ def test_canaries_and_the_capacity_error(ctx, geo):
             d_tab = ctx.workspace("quote_table_canary", tab_canary.nbytes)
             ctx.h2d(d_low.ptr, low_canary)
             ctx.h2d(d_tab.ptr, tab_canary)
-            ctx.record_ends_blocked_async(addr, len(buf), buf_base, begin, end, 34, carry, d_low.ptr, cap, d_tab.ptr, nt)
+            ctx.records_async(addr, len(buf), buf_base, begin, end, quote=34, carry=carry, form="u16b", d_out=d_low.ptr,
+                              cap=cap, d_table=d_tab.ptr, table_cap=nt)
             if cap < len(exp):
                 with pytest.raises(DPCapacityError) as ei:
-                    ctx.record_ends_result()
+                    ctx.records_result()
                 assert (ei.value.needed, ei.value.n_quotes, ei.value.n_newlines) == (len(exp), eq, en)
             else:
-                assert ctx.record_ends_result() == (len(exp), eq, en)
+                assert ctx.records_result()[:3] == (len(exp), eq, en)
             low = ctx.d2h(np.empty_like(low_canary), d_low.ptr)
             tab = ctx.d2h(np.empty_like(tab_canary), d_tab.ptr)
             assert np.array_equal(low[:cap], (exp[:cap] & np.uint64(0xFFFF)).astype(np.uint16))
@@ -173,8 +175,9 @@ def test_canaries_and_the_capacity_error(ctx, geo):
     assert len(low) == len(record_ends(buf[9:])[0])
     # the count-only call of this entry point: no low words, the table all the same
     ctx.h2d(d_tab.ptr, tab_canary)
-    ctx.record_ends_blocked_async(addr, len(buf), buf_base, begin, end, 34, 0, 0, 0, d_tab.ptr, nt)
-    assert ctx.record_ends_result()[0] == len(low)
+    ctx.records_async(addr, len(buf), buf_base, begin, end, quote=34, carry=0, form="u16b", d_out=0, cap=0,
+                      d_table=d_tab.ptr, table_cap=nt)
+    assert ctx.records_result().n == len(low)
     assert np.array_equal(ctx.d2h(np.empty(nt, np.uint64), d_tab.ptr), table)
 
 
@@ -186,12 +189,16 @@ def test_misaligned_address_and_bad_tables_are_refused(ctx, geo):
     tab = ctx.workspace("record_blocks", 1 << 16)
     ok = (addr, 4000, buf_base, begin, begin + 4000, 34, 0, out.ptr, 4096, tab.ptr, 1)
 
+    def launch(d_buf, buf_len, buf_base, begin, end, quote, carry, d_low, cap, d_table, table_cap):
+        ctx.records_async(d_buf, buf_len, buf_base, begin, end, quote=quote, carry=carry, form="u16b", d_out=d_low,
+                          cap=cap, d_table=d_table, table_cap=table_cap)
+
     def refused(**kw):
         args = dict(zip(("d_buf", "buf_len", "buf_base", "begin", "end", "quote", "carry", "d_low", "cap", "d_table",
                          "table_cap"), ok))
         args.update(kw)
         with pytest.raises(DPScanError):
-            ctx.record_ends_blocked_async(*args.values())
+            launch(*args.values())
     for off in (1, 8, 15):
         refused(d_buf=addr + off)                        # the device address of begin is not congruent to begin mod 16
     refused(buf_base=buf_base + 1, begin=begin + 1, end=begin + 4001)       # the same bytes, named one offset higher
@@ -204,9 +211,9 @@ def test_misaligned_address_and_bad_tables_are_refused(ctx, geo):
     refused(quote=10)
     refused(carry=2)
     refused(end=begin + 5000)                            # past the buffer
-    ctx.record_ends_blocked_async(*ok)                   # nothing above left a launch in flight
-    assert ctx.record_ends_result() == (4000, 0, 4000)
-    low, table, _, _ = ctx.record_ends_blocked(addr + 5, 4000, buf_base, begin + 77, begin + 77)   # empty: no rule
+    launch(*ok)                                          # nothing above left a launch in flight
+    assert ctx.records_result()[:3] == (4000, 0, 4000)
+    low, table, _, _, _, _ = ctx.records(addr + 5, 4000, buf_base, begin + 77, begin + 77, form="u16b")  # empty: no rule
     assert len(low) == 0 and len(table) == 0
 
 
@@ -218,9 +225,9 @@ def test_forms_agree_and_contexts_are_reusable(ctx, geo):
     def both(c, buf, lo, begin, carry):
         addr, buf_base = place(c, buf, lo, begin)
         end = begin + len(buf) - lo
-        u64 = c.record_ends(addr, len(buf), buf_base, begin, end, carry=carry)[0]
-        low, table, _, _ = c.record_ends_blocked(addr, len(buf), buf_base, begin, end, carry=carry)
-        again = c.record_ends(addr, len(buf), buf_base, begin, end, carry=carry)[0]
+        u64 = c.records(addr, len(buf), buf_base, begin, end, carry=carry).ends
+        low, table, _, _, _, _ = c.records(addr, len(buf), buf_base, begin, end, carry=carry, form="u16b")
+        again = c.records(addr, len(buf), buf_base, begin, end, carry=carry).ends
         dec = BlockedOffsets(low, table, begin >> 16).to_u64()
         assert np.array_equal(dec, u64) and np.array_equal(again, u64)
         assert np.array_equal(u64, record_ends(buf[lo:], base=begin, carry=carry)[0])

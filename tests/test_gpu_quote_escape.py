@@ -40,10 +40,9 @@ def launch(ctx, c, addr, form):
     """One escaped launch of a case: (out..., n_out, n_quotes, n_newlines, 0, toggles), shaped like C.model's."""
     a = (addr, len(c["buf"]), c["base"], c["begin"], c["end"])
     kw = dict(quote=c["quote"], carry=c["carry"], escape=c["escape"], esc_carry=c["esc_carry"], scope=c["scope"])
+    out, table, nq, nn, tog, _ = ctx.records(*a, form=form, **kw)
     if form == "u16b":
-        low, table, nq, nn, tog = ctx.record_ends_blocked_escaped(*a, **kw)
-        return low, table, len(low), nq, nn, 0, tog
-    out, nq, nn, tog = ctx.record_ends_escaped(*a, u64=form == "u64", **kw)
+        return out, table, len(out), nq, nn, 0, tog
     return out, len(out), nq, nn, 0, tog
 
 
@@ -61,8 +60,9 @@ def check(ctx, c, exp=None, forms=None, with_model=True):
         if with_model:
             m = C.model(emu, c, form)
             assert len(m) == len(r) and all(np.array_equal(x, y) for x, y in zip(m, r)), (c["name"], form)
-    assert ctx.record_counts_escaped(addr, len(c["buf"]), c["base"], c["begin"], c["end"], c["quote"], c["carry"],
-                                     c["escape"], c["esc_carry"], c["scope"]) == (len(ends), nq, nn, tog)
+    counts = ctx.records(addr, len(c["buf"]), c["base"], c["begin"], c["end"], quote=c["quote"], carry=c["carry"],
+                         escape=c["escape"], esc_carry=c["esc_carry"], scope=c["scope"], form="count")
+    assert (counts.n, counts.n_quotes, counts.n_newlines, counts.toggles) == (len(ends), nq, nn, tog)
 
 
 def test_every_escape_byte_value_at_every_chunk_position(ctx):
@@ -176,13 +176,13 @@ def test_an_absent_escape_byte_equals_the_plain_launch(ctx):
     c = C.case(d, begin=9, carry=1, escape=C.E, name="absent")
     addr = place(ctx, c)
     a = (addr, len(d), 0, 9, len(d))
-    for u64 in (False, True):
-        out, nq, nn = ctx.record_ends(*a, quote=C.Q, carry=1, u64=u64)
+    for form in ("u32", "u64"):
+        out, _, nq, nn, _, _ = ctx.records(*a, quote=C.Q, carry=1, form=form)
         for scope in ("all", "quoted"):
-            eo, enq, enn, tog = ctx.record_ends_escaped(*a, quote=C.Q, carry=1, escape=C.E, scope=scope, u64=u64)
+            eo, _, enq, enn, tog, _ = ctx.records(*a, quote=C.Q, carry=1, escape=C.E, scope=scope, form=form)
             assert eo.dtype == out.dtype and eo.tobytes() == out.tobytes() and (enq, enn, tog) == (nq, nn, nq)
-    low, table, nq, nn = ctx.record_ends_blocked(*a, quote=C.Q, carry=1)
-    elow, etable, enq, enn, tog = ctx.record_ends_blocked_escaped(*a, quote=C.Q, carry=1, escape=C.E)
+    low, table, nq, nn, _, _ = ctx.records(*a, quote=C.Q, carry=1, form="u16b")
+    elow, etable, enq, enn, tog, _ = ctx.records(*a, quote=C.Q, carry=1, escape=C.E, form="u16b")
     assert elow.tobytes() == low.tobytes() and etable.tobytes() == table.tobytes() and (enq, enn, tog) == (nq, nn, nq)
 
 
@@ -194,18 +194,18 @@ def test_entry_points_refuse_bad_escape_arguments(ctx):
     for kw in (dict(escape=C.Q), dict(escape=10), dict(escape=256), dict(escape=92, esc_carry=2),
                dict(escape=92, quote=10), dict(escape=92, carry=2)):
         with pytest.raises(DPScanError) as ei:
-            ctx.record_ends_escaped(*a, **kw)
+            ctx.records(*a, **kw)
         assert ei.value.code == _quote.DQ_ERR_INVALID
         with pytest.raises(DPScanError) as ei:
-            ctx.record_ends_blocked_escaped(*a, **kw)
+            ctx.records(*a, form="u16b", **kw)
         assert ei.value.code == _quote.DQ_ERR_INVALID
     q, h = ctx._quote_ctx()
     import ctypes
     rc = q.dq_records_esc_async(h, ctypes.c_void_p(addr), len(d), 0, 0, len(d), 34, 0, 92, 0, 2, None, 1, 0)
     assert rc == _quote.DQ_ERR_INVALID                   # an unknown flags bit
     with pytest.raises(ValueError):
-        ctx.record_ends_escaped(*a, scope="some")
-    assert len(ctx.record_ends_escaped(*a)[0]) == len(loop_record_ends(d)[0])    # the ctx is usable afterwards
+        ctx.records(*a, escape=92, scope="some")
+    assert len(ctx.records(*a, escape=92).ends) == len(loop_record_ends(d)[0])   # the ctx is usable afterwards
 
 
 def test_a_run_beyond_the_bound_is_reported_at_once(ctx):
@@ -218,7 +218,7 @@ def test_a_run_beyond_the_bound_is_reported_at_once(ctx):
     ctx.sync()
     t0 = time.perf_counter()
     with pytest.raises(_quote.DPEscapeRunError) as ei:
-        ctx.record_ends_escaped(addr, len(d), 0, 0, len(d))
+        ctx.records(addr, len(d), 0, 0, len(d), escape=92)
     dt = time.perf_counter() - t0
     assert ei.value.code == _quote.DQ_ERR_ESCAPE_RUN
     assert dt < 1.0, f"{dt:.3f} s"

@@ -4,11 +4,13 @@ definition (tests/_quote_model.py), the stored form's round trip through store_r
 in-memory store, the record partition strategies on both stored forms, attributes written before the form existed,
 and the refusal of other formats.  tests/test_gpu_quote_blocked.py runs the kernel."""
 import ctypes
+import functools
 import threading
 
 import numpy as np
 import pytest
 
+import _fake_scan
 from _quote_model import record_ends
 from dataplug_amd import synth
 from dataplug_amd.cloudobject import CloudObject
@@ -33,77 +35,12 @@ def test_blocked_entry_point_is_exported_and_refuses_a_null_context():
 
 
 # ------------------------------------------------------------------------------------------------ the fake device layer
-class FakeBuffer:
-    def __init__(self, ptr):
-        self.ptr = ptr
+def _note(c):
+    """The fake device layer's emitting launches as these tests read them: (form, begin, end, carry)."""
+    return None if c.form == "count" or c.relaunch else (c.form, c.begin, c.end, c.carry)
 
 
-class FakeContext:
-    """What record_index_object uses of a ScanContext, over numpy memory, the scans from the definition."""
-    BASE = 1 << 20                                       # device address of the context's memory, 16-byte aligned
-
-    def __init__(self, layer):
-        self.layer = layer
-        self.mem = np.zeros(0, np.uint8)
-
-    def workspace(self, name, nbytes, placed=False):
-        assert name == "input"
-        if len(self.mem) < nbytes:
-            self.mem = np.zeros(nbytes, np.uint8)
-        return FakeBuffer(self.BASE)
-
-    def _ends(self, d_buf, buf_len, buf_base, begin, end, quote, carry):
-        assert buf_base <= begin <= end <= buf_base + buf_len and d_buf + buf_len <= self.BASE + len(self.mem)
-        a = d_buf - self.BASE + (begin - buf_base)
-        return record_ends(self.mem[a:a + end - begin], begin, quote, carry)
-
-    def record_counts(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0):
-        if self.layer.fail_counts_at == begin:
-            raise RuntimeError("fake: record_counts failed")
-        ends, nq, nn = self._ends(d_buf, buf_len, buf_base, begin, end, quote, carry)
-        return len(ends), nq, nn
-
-    def record_ends(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, u64=True, cap=None):
-        assert u64
-        self.layer.note("u64", begin, end, carry)
-        return self._ends(d_buf, buf_len, buf_base, begin, end, quote, carry)
-
-    def record_ends_blocked(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, cap=None):
-        # the alignment rule of dq_records_blocked_async
-        assert (d_buf + (begin - buf_base)) % 16 == begin % 16, "device address not congruent to begin mod 16"
-        self.layer.note("u16b", begin, end, carry)
-        ends, nq, nn = self._ends(d_buf, buf_len, buf_base, begin, end, quote, carry)
-        nt = ((end - 1) >> 16) - (begin >> 16) + 1
-        bounds = np.arange(begin >> 16, (begin >> 16) + nt, dtype=np.uint64) << np.uint64(16)
-        table = np.searchsorted(ends, bounds, side="left").astype(np.uint64)       # this launch's ends below each block
-        return (ends & np.uint64(0xFFFF)).astype(np.uint16), table, nq, nn
-
-
-class FakeDevices:
-    def __init__(self, monkeypatch, devs):
-        self.tls = threading.local()
-        self.lock = threading.Lock()
-        self.calls = []
-        self.fail_counts_at = None
-        monkeypatch.setattr(scan_objects, "get_context", self.get_context)
-        monkeypatch.setattr(scan_objects, "fetch_to_device", self.fetch_to_device)
-        monkeypatch.setattr(scan_objects, "devices", lambda max_devices=None, co=None: list(devs))
-
-    def note(self, *call):
-        with self.lock:
-            self.calls.append(call)
-
-    def get_context(self, device=0, slot=0):
-        ctxs = self.tls.__dict__.setdefault("ctxs", {})
-        if device not in ctxs:
-            ctxs[device] = FakeContext(self)
-        return ctxs[device]
-
-    def fetch_to_device(self, ctx, storage, bucket, key, lo, hi, d_ptr, **kw):
-        raw = storage.get_object(Bucket=bucket, Key=key, Range=f"bytes={lo}-{hi - 1}")["Body"].read()
-        assert len(raw) == hi - lo and d_ptr % 16 == lo % 16
-        a = d_ptr - ctx.BASE
-        ctx.mem[a:a + hi - lo] = np.frombuffer(raw, np.uint8)
+FakeDevices = functools.partial(_fake_scan.FakeDevices, note=_note)
 
 
 def _co(data: bytes, key: str, name: str):

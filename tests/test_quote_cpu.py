@@ -5,6 +5,7 @@ the kernel).  The last section runs scan.objects.record_index_object itself -- t
 the capacity choice and the release of waiting parts after a failure -- over a numpy-backed fake of the device layer."""
 import csv as pycsv
 import ctypes
+import functools
 import io
 import json
 import os
@@ -17,6 +18,7 @@ import time
 import numpy as np
 import pytest
 
+import _fake_scan
 from _quote_model import record_ends
 from dataplug_amd import build as B
 from dataplug_amd import synth
@@ -271,78 +273,12 @@ def test_missing_record_index_is_a_key_error_and_default_preprocess_is_unchanged
 
 
 # ------------------------------------------------------------------------------------------------ record_index_object
-class FakeBuffer:
-    def __init__(self, ptr):
-        self.ptr = ptr
+def _note(c):
+    """The fake device layer's launches as these tests read them: ("counts" | "ends", begin, end, carry, cap)."""
+    return "counts" if c.form == "count" else "ends", c.begin, c.end, c.carry, c.cap
 
 
-class FakeContext:
-    """What record_index_object uses of a ScanContext, over numpy memory: workspace, record_counts and record_ends,
-    the two scans from the model, honouring carry and cap (a too small cap costs a second launch, as on the GPU)."""
-    BASE = 1 << 20                                       # device address of the context's memory, 16-byte aligned
-
-    def __init__(self, layer):
-        self.layer = layer
-        self.mem = np.zeros(0, np.uint8)
-
-    def workspace(self, name, nbytes, placed=False):
-        assert name == "input"
-        if len(self.mem) < nbytes:
-            self.mem = np.zeros(nbytes, np.uint8)
-        return FakeBuffer(self.BASE)
-
-    def _bytes(self, d_buf, buf_len, buf_base, begin, end):
-        assert buf_base <= begin <= end <= buf_base + buf_len and d_buf + buf_len <= self.BASE + len(self.mem)
-        a = d_buf - self.BASE + (begin - buf_base)
-        return self.mem[a:a + end - begin]
-
-    def record_counts(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0):
-        self.layer.note("counts", begin, end, carry, 0)
-        if self.layer.fail_counts_at == begin:
-            raise RuntimeError("fake: record_counts failed")
-        ends, nq, nn = record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
-        return len(ends), nq, nn
-
-    def record_ends(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, u64=True, cap=None):
-        assert u64
-        ends, nq, nn = record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
-        if cap is None:
-            cap = (end - begin) // 16 + 1024
-        self.layer.note("ends", begin, end, carry, cap)
-        if len(ends) > cap:                              # DPCapacityError, then the launch sized by the count
-            self.layer.note("ends", begin, end, carry, len(ends))
-        return ends, nq, nn
-
-
-class FakeDevices:
-    """scan.objects' device layer replaced: get_context (one context per thread and device, like the real one),
-    fetch_to_device (the object's bytes into the context's numpy memory) and devices."""
-
-    def __init__(self, monkeypatch, devs):
-        self.tls = threading.local()
-        self.lock = threading.Lock()
-        self.calls = []
-        self.fail_counts_at = None
-        monkeypatch.setattr(scan_objects, "get_context", self.get_context)
-        monkeypatch.setattr(scan_objects, "fetch_to_device", self.fetch_to_device)
-        monkeypatch.setattr(scan_objects, "devices", lambda max_devices=None, co=None: list(devs))
-
-    def note(self, *call):
-        with self.lock:
-            self.calls.append(call)
-
-    def get_context(self, device=0, slot=0):
-        ctxs = self.tls.__dict__.setdefault("ctxs", {})
-        if device not in ctxs:
-            ctxs[device] = FakeContext(self)
-        return ctxs[device]
-
-    def fetch_to_device(self, ctx, storage, bucket, key, lo, hi, d_ptr, **kw):
-        raw = storage.get_object(Bucket=bucket, Key=key, Range=f"bytes={lo}-{hi - 1}")["Body"].read()
-        assert len(raw) == hi - lo and d_ptr % 16 == lo % 16
-        a = d_ptr - ctx.BASE
-        ctx.mem[a:a + hi - lo] = np.frombuffer(raw, np.uint8)
-
+FakeDevices = functools.partial(_fake_scan.FakeDevices, note=_note)
 
 CHAIN_BYTES, CHAIN_PART = (1 << 18) + 77, 1 << 14
 

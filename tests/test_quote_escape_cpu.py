@@ -3,13 +3,14 @@ over a numpy-backed fake of the device layer whose scans are the byte loop (test
 an escape run, right after an odd run and inside a quoted field, the chain fed by toggles, today's calls when no escape
 is given -- and preprocess / partition over the in-memory store with the scan stubbed by the loop."""
 import csv as pycsv
+import functools
 import io
-import threading
 
 import numpy as np
 import pytest
 
-from _escape_loop import blocked, loop_quote_bytes, loop_record_ends
+import _fake_scan
+from _escape_loop import blocked, loop_record_ends
 from _quote_model import record_ends
 from dataplug_amd import synth
 from dataplug_amd.cloudobject import CloudObject
@@ -49,96 +50,17 @@ def test_stamp_lists_six_instantiations_without_scratch():
 
 
 # ------------------------------------------------------------------------------------------------ the fake device layer
-class FakeBuffer:
-    def __init__(self, ptr):
-        self.ptr = ptr
+def _note(c):
+    """The fake device layer's launches as these tests read them: ("counts" | form, begin, end, carry) of a plain
+    launch, (.. + "_esc", begin, end, carry, esc_carry, scope) of an escaped one."""
+    if c.relaunch:
+        return None
+    name = "counts" if c.form == "count" else c.form
+    return (name, c.begin, c.end, c.carry) if c.escape is None else \
+        (name + "_esc", c.begin, c.end, c.carry, c.esc_carry, c.scope)
 
 
-class FakeContext:
-    """What record_index_object uses of a ScanContext, over numpy memory: the plain scans from the parity rule, the
-    escaped ones from the byte loop."""
-    BASE = 1 << 20
-
-    def __init__(self, layer):
-        self.layer = layer
-        self.mem = np.zeros(0, np.uint8)
-
-    def workspace(self, name, nbytes, placed=False):
-        assert name == "input"
-        if len(self.mem) < nbytes:
-            self.mem = np.zeros(nbytes, np.uint8)
-        return FakeBuffer(self.BASE)
-
-    def _bytes(self, d_buf, buf_len, buf_base, begin, end):
-        assert buf_base <= begin <= end <= buf_base + buf_len and d_buf + buf_len <= self.BASE + len(self.mem)
-        a = d_buf - self.BASE + (begin - buf_base)
-        return self.mem[a:a + end - begin]
-
-    # today's methods, with today's arguments only
-    def record_counts(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0):
-        self.layer.note("counts", begin, end, carry)
-        ends, nq, nn = record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
-        return len(ends), nq, nn
-
-    def record_ends(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, u64=True, cap=None):
-        self.layer.note("u64", begin, end, carry)
-        return record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
-
-    def record_ends_blocked(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, cap=None):
-        self.layer.note("u16b", begin, end, carry)
-        ends, nq, nn = record_ends(self._bytes(d_buf, buf_len, buf_base, begin, end), begin, quote, carry)
-        return blocked(ends, begin, end) + (nq, nn)
-
-    # the escaped counterparts
-    def _loop(self, d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry, scope):
-        d = self._bytes(d_buf, buf_len, buf_base, begin, end)
-        ends, tog, _, _ = loop_record_ends(d, begin, end, quote, escape, carry, esc_carry, scope, base=begin)
-        return ends, loop_quote_bytes(d, quote=quote), int(np.count_nonzero(d == 10)), tog
-
-    def record_counts_escaped(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, escape=92, esc_carry=0,
-                              scope="all"):
-        self.layer.note("counts_esc", begin, end, carry, esc_carry, scope)
-        ends, nq, nn, tog = self._loop(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry, scope)
-        return len(ends), nq, nn, tog
-
-    def record_ends_escaped(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, escape=92, esc_carry=0,
-                            scope="all", u64=True, cap=None):
-        assert u64
-        self.layer.note("u64_esc", begin, end, carry, esc_carry, scope)
-        return self._loop(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry, scope)
-
-    def record_ends_blocked_escaped(self, d_buf, buf_len, buf_base, begin, end, quote=34, carry=0, escape=92,
-                                    esc_carry=0, scope="all", cap=None):
-        assert (d_buf + (begin - buf_base)) % 16 == begin % 16
-        self.layer.note("u16b_esc", begin, end, carry, esc_carry, scope)
-        ends, nq, nn, tog = self._loop(d_buf, buf_len, buf_base, begin, end, quote, carry, escape, esc_carry, scope)
-        return blocked(ends, begin, end) + (nq, nn, tog)
-
-
-class FakeDevices:
-    def __init__(self, monkeypatch, devs):
-        self.tls = threading.local()
-        self.lock = threading.Lock()
-        self.calls = []
-        monkeypatch.setattr(scan_objects, "get_context", self.get_context)
-        monkeypatch.setattr(scan_objects, "fetch_to_device", self.fetch_to_device)
-        monkeypatch.setattr(scan_objects, "devices", lambda max_devices=None, co=None: list(devs))
-
-    def note(self, *call):
-        with self.lock:
-            self.calls.append(call)
-
-    def get_context(self, device=0, slot=0):
-        ctxs = self.tls.__dict__.setdefault("ctxs", {})
-        if device not in ctxs:
-            ctxs[device] = FakeContext(self)
-        return ctxs[device]
-
-    def fetch_to_device(self, ctx, storage, bucket, key, lo, hi, d_ptr, **kw):
-        raw = storage.get_object(Bucket=bucket, Key=key, Range=f"bytes={lo}-{hi - 1}")["Body"].read()
-        assert len(raw) == hi - lo and d_ptr % 16 == lo % 16
-        a = d_ptr - ctx.BASE
-        ctx.mem[a:a + hi - lo] = np.frombuffer(raw, np.uint8)
+FakeDevices = functools.partial(_fake_scan.FakeDevices, note=_note)
 
 
 def _co(data: bytes, key: str, name: str):

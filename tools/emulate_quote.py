@@ -662,8 +662,8 @@ def run(buf, dev_addr: int = 0, buf_base: int = 0, begin: Optional[int] = None, 
         quote: int = 34, carry: int = 0, u64: bool = True, cap: Optional[int] = None, schedule="sequential",
         mutate: Optional[str] = None, outside: bytes = b'"\n', stats: Optional[dict] = None,
         fmt: Optional[str] = None, escape: Optional[int] = None, esc_carry: int = 0, escape_scope: str = "all"):
-    """One launch, as ScanContext.record_ends_async + record_ends_result see it:
-    (offsets, n_out, n_quotes, n_newlines, err_bits); with ``fmt="u16b"`` as record_ends_blocked_async does:
+    """One launch, as ScanContext.records_async + records_result see it:
+    (offsets, n_out, n_quotes, n_newlines, err_bits); with ``fmt="u16b"`` as ``form="u16b"`` does:
     (low, table, n_out, n_quotes, n_newlines, err_bits)."""
     if fmt not in (None, "u16b"):
         raise ValueError(f"fmt={fmt!r}: None (the uint32 / uint64 forms, by u64=) or 'u16b'")
