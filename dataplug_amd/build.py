@@ -1,4 +1,4 @@
-"""Build libdpscan.so, libdpquote.so and libdpfai.so in-tree for gfx950:  python -m dataplug_amd.build
+"""Build libdpscan.so, libdpquote.so, libdpfai.so and libdpvpos.so in-tree for gfx950:  python -m dataplug_amd.build
 
 The scan library is compiled with -save-temps and the ISA guard (dataplug_amd/isa_guard.py) checks that exact
 device assembly: every kernel, no touched in-flight load destination, no scratch segment.  Only a library that
@@ -28,6 +28,9 @@ QUOTE_REQUIRED = ("quote_kernel",)                         # the kernels libdpqu
 FAI_SRC = os.path.join(HERE, "csrc", "dpfai.hip")          # per-sequence counts of a FASTA .fai (include/dpfai.h)
 FAI_OUT = os.path.join(HERE, "lib", "libdpfai.so")
 FAI_REQUIRED = ("fai_count_kernel", "fai_name_kernel")     # the kernels libdpfai.so must contain
+VPOS_SRC = os.path.join(HERE, "csrc", "dpvpos.hip")        # CHROM / POS parse of a VCF body (include/dpvpos.h)
+VPOS_OUT = os.path.join(HERE, "lib", "libdpvpos.so")
+VPOS_REQUIRED = ("vpos_parse_kernel", "vpos_reduce_kernel", "vpos_name_kernel")   # what libdpvpos.so must contain
 GZ_SRC = os.path.join(HERE, "csrc", "dpgz.c")
 GZ_PAR_SRC = os.path.join(HERE, "csrc", "dpgz_par.c")     # parallel inflate of one gzip stream
 GZ_OUT = os.path.join(HERE, "lib", "libdpgz.so")            # host-side gzip access-point index (zlib)
@@ -98,6 +101,12 @@ def build_fai(verbose: bool = False) -> str:
     return build(verbose=verbose, out=FAI_OUT, src=FAI_SRC, required=FAI_REQUIRED)
 
 
+def build_vpos(verbose: bool = False) -> str:
+    """libdpvpos.so: the same hipcc line with -save-temps, the ISA guard on that exact assembly (its own kernel
+    list), installed with its ``.isa.json`` stamp only on "ok"."""
+    return build(verbose=verbose, out=VPOS_OUT, src=VPOS_SRC, required=VPOS_REQUIRED)
+
+
 def build_gz() -> str:
     os.makedirs(os.path.dirname(GZ_OUT), exist_ok=True)
     cc = os.environ.get("CC", "gcc")
@@ -112,3 +121,4 @@ if __name__ == "__main__":
     print(build(verbose="-v" in sys.argv, diag="--diag" in sys.argv))
     print(build_quote(verbose="-v" in sys.argv))
     print(build_fai(verbose="-v" in sys.argv))
+    print(build_vpos(verbose="-v" in sys.argv))

@@ -6,16 +6,25 @@ vcf.py:19-67) and adds the offsets of every '\\n' in ``[body_offset, size)``, sc
 parts (one or more per GPU), stored at ``<key>.lines`` (``index_format="auto"``: the u8s form, or u16b for bodies
 with fewer than one newline per 128 bytes; ``_lines.store_line_index``).  ``partition_num_chunks`` gives
 the reference's ranges and a ``get()`` with identical output (formulas: ``_lines.vcf_body``).
+
+Opt-in ``extra_args={"pos_index": True}``: a position index (include/dpvpos.h) is built on the GPU -- the POS of every
+``pos_index_every``-th body line (uint32 LE) at ``<key>.pos`` and a table of the contig runs at ``<key>.contigs`` in
+the meta bucket (attributes ``pos_index_key``, ``pos_index_every``, ``contigs_key``, ``num_contigs``,
+``num_body_lines``); ``load_contigs``, ``fetch_region``, ``partition_contigs_strategy`` and
+``partition_regions_strategy`` read it.  Without the key every stored byte and attribute is as before.
 """
 from __future__ import annotations
 
 import logging
 import re
 from math import ceil
-from typing import TYPE_CHECKING, Dict, List, Optional, Union
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
 
 from ...entities import CloudDataFormat, CloudObjectSlice, PartitioningStrategy
 from ...preprocessing.metadata import PreprocessingMetadata
+from ...scan.vpos import VcfFormatError  # noqa: F401  (raised by preprocess with pos_index)
 from .._lines import LineIndex, SliceError, index_object, slice_error, vcf_body
 
 if TYPE_CHECKING:
@@ -59,13 +68,43 @@ def parse_vcf_header(f):
     return header, meta, columns, pos
 
 
-def preprocess_vcf(cloud_object: "CloudObject", line_index: bool = True, index_format: str = "auto") -> PreprocessingMetadata:
+POS_SUFFIX, CONTIGS_SUFFIX = ".pos", ".contigs"
+
+
+def preprocess_vcf(cloud_object: "CloudObject", line_index: bool = True, index_format: str = "auto",
+                   pos_index: bool = False, pos_index_every: int = 128) -> PreprocessingMetadata:
     with cloud_object.open("rb") as f:
         header, meta, columns, body_offset = parse_vcf_header(f)
     attrs = {"columns": columns, "vcf_attributes": meta, "body_offset": body_offset}
     if line_index:
         attrs.update(index_object(cloud_object, body_offset, index_format))
-    return PreprocessingMetadata(attributes=attrs, metadata="\n".join(header).encode("utf-8"))
+    out = PreprocessingMetadata(attributes=attrs, metadata="\n".join(header).encode("utf-8"))
+    if pos_index:
+        if not line_index:
+            raise ValueError("pos_index needs the newline index: line_index must be True")
+        _with_pos_index(cloud_object, out, body_offset, pos_index_every)
+    return out
+
+
+def _with_pos_index(cloud_object: "CloudObject", meta: PreprocessingMetadata, body_offset: int, every: int) -> None:
+    """Build and store the position index and add its attributes to ``meta``.  On ``VcfFormatError`` the header, the
+    newline index and the attributes are stored as they would be without ``pos_index`` before the error goes on."""
+    from ...preprocessing.handler import upload_metadata
+    from ...scan import objects as scan_objects
+    from ...scan import vpos
+    from ...version import __version__
+    try:
+        samples, names, rows, n_lines = scan_objects.pos_index_object(cloud_object, body_offset, every)
+    except VcfFormatError:
+        upload_metadata(cloud_object, meta)
+        raise
+    st, bucket = cloud_object.storage, cloud_object.meta_path.bucket
+    pkey, ckey = cloud_object.path.key + POS_SUFFIX, cloud_object.path.key + CONTIGS_SUFFIX
+    user = {"dataplug": __version__}
+    st.put_object(Body=np.ascontiguousarray(samples, "<u4").tobytes(), Bucket=bucket, Key=pkey, Metadata=user)
+    st.put_object(Body=vpos.contigs_text(names, rows), Bucket=bucket, Key=ckey, Metadata=user)
+    meta.attributes = dict(meta.attributes, pos_index_key=pkey, pos_index_every=int(every), contigs_key=ckey,
+                           num_contigs=len(names), num_body_lines=int(n_lines))
 
 
 def preprocess_vcf_gz(cloud_object: "CloudObject") -> PreprocessingMetadata:
@@ -79,6 +118,11 @@ class VCF:
     body_offset: int
     num_lines: int
     line_index_key: str
+    pos_index_key: str
+    pos_index_every: int
+    contigs_key: str
+    num_contigs: int
+    num_body_lines: int
 
 
 class VCFSlice(CloudObjectSlice):
@@ -123,4 +167,145 @@ def partition_num_chunks(cloud_object: "CloudObject", num_chunks: int, padding: 
             body, err = None, e
         out.append(VCFSlice(range_0=r0, range_1=r1, chunk_id=i, num_chunks=num_chunks, padding=padding,
                             body=body, error=err))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ position index (pos_index)
+def load_contigs(cloud_object: "CloudObject"):
+    """(names, rows) of the stored contig table: the names as a list of bytes and ``rows`` a structured array with the
+    fields first_line, num_lines, offset, end, min_pos, max_pos (``scan.vpos.CONTIG_DTYPE``).  KeyError when the
+    object was preprocessed without ``pos_index``."""
+    from ...scan import vpos
+    key = getattr(cloud_object.attributes, "contigs_key", None)
+    if not isinstance(key, str) or not key.endswith(CONTIGS_SUFFIX):     # (unset: the class's annotation)
+        raise KeyError("pos_index: this object has no position index; preprocess it with "
+                       "extra_args={'pos_index': True}")
+    res = cloud_object.storage.get_object(Bucket=cloud_object.meta_path.bucket, Key=key)
+    return vpos.parse_contigs(res["Body"].read())
+
+
+def _contig(cloud_object, chrom):
+    names, rows = load_contigs(cloud_object)
+    chrom = chrom.encode() if isinstance(chrom, str) else bytes(chrom)
+    try:
+        return rows[names.index(chrom)]
+    except ValueError:
+        raise KeyError(f"pos_index: no contig named {chrom!r}") from None
+
+
+def _samples(cloud_object, j0: int, j1: int) -> np.ndarray:
+    """Samples [j0, j1) of the stored ``<key>.pos`` (one ranged GET)."""
+    if j1 <= j0:
+        return np.zeros(0, np.uint32)
+    res = cloud_object.storage.get_object(Bucket=cloud_object.meta_path.bucket,
+                                          Key=cloud_object.attributes.pos_index_key,
+                                          Range=f"bytes={4 * j0}-{4 * j1 - 1}")
+    return np.frombuffer(res["Body"].read(), "<u4")
+
+
+def _line_offset(lines: LineIndex, body_offset: int, ordinal: int, size: int) -> int:
+    """The byte offset of body line ``ordinal`` (the line count itself: the end of the body's last line)."""
+    if ordinal == 0:
+        return body_offset
+    return min(size, lines.value(ordinal - 1) + 1) if ordinal - 1 < lines.count else size
+
+
+def _window_positions(cloud_object, buf: bytes, w0: int):
+    """(byte offsets, POS) of the lines of ``buf`` = object bytes from ``w0``, which starts at a line start."""
+    nl = np.flatnonzero(np.frombuffer(buf, np.uint8) == 10)
+    starts = np.concatenate([[0], nl + 1])
+    starts = starts[starts < len(buf)]
+    pos = np.empty(len(starts), np.int64)
+    for k, s in enumerate(starts.tolist()):
+        try:
+            pos[k] = int(buf[s:s + 1024].split(b"\t", 2)[1])
+        except (IndexError, ValueError):
+            raise ValueError(f"pos_index: the line at byte {w0 + s} of {cloud_object.path.key!r} has no numeric POS: "
+                             f"the object does not match its position index (changed after preprocess?)") from None
+    return starts + w0, pos
+
+
+def region_range(cloud_object: "CloudObject", chrom, start: Optional[int] = None, end: Optional[int] = None,
+                 lines: Optional[LineIndex] = None, fetch: bool = False):
+    """(first byte, one past the last byte, candidate byte range, candidate bytes or None) of the lines of contig
+    ``chrom`` with start <= POS <= end.  The candidate lines [a, b) come from the samples
+    (``scan.vpos.candidate_lines``) and their byte range from the newline index.  Only the lines of the first and of
+    the last sample interval of the candidates are parsed: the first line with POS >= start lies in [a, a + K] and
+    the first with POS > end in [b - K, b).  A side that is open is the contig's own bound and is not parsed, so an
+    open region reads nothing of the object.  ``fetch``: one ranged GET of the whole candidate range, returned and
+    used for the two windows; otherwise each window is a ranged GET of its own."""
+    from ...scan import vpos
+    row = _contig(cloud_object, chrom)
+    size, bo = cloud_object.size, int(cloud_object["body_offset"])
+    every = int(cloud_object.attributes.pos_index_every)
+    l0, l1 = int(row["first_line"]), int(row["first_line"]) + int(row["num_lines"])
+    a, b = l0, l1
+    if start is not None or end is not None:
+        j0, j1 = -(-l0 // every), -(-l1 // every)                     # the samples whose ordinals lie in [l0, l1)
+        a, b = vpos.candidate_lines(_samples(cloud_object, j0, j1), j0, every, l0, l1, start, end)
+    if a == l0 and b == l1:
+        c0, c1 = int(row["offset"]), int(row["end"])
+    else:
+        lines = lines or LineIndex.of(cloud_object)
+        c0, c1 = _line_offset(lines, bo, a, size), _line_offset(lines, bo, b, size)
+    if c1 <= c0:
+        return c0, c0, (c0, c0), b"" if fetch else None
+    get = lambda x, y: cloud_object.storage.get_object(Bucket=cloud_object.path.bucket, Key=cloud_object.path.key,
+                                                       Range=f"bytes={x}-{y - 1}")["Body"].read()
+    raw = get(c0, c1) if fetch else None
+
+    def window(i0, i1):
+        """The lines [i0, i1) of the candidates: (byte offsets, POS, the window's end)."""
+        nonlocal lines
+        if i0 == a and i1 == b:
+            w0, w1 = c0, c1
+        else:
+            lines = lines or LineIndex.of(cloud_object)
+            w0 = c0 if i0 == a else _line_offset(lines, bo, i0, size)
+            w1 = c1 if i1 == b else _line_offset(lines, bo, i1, size)
+        buf = raw[w0 - c0:w1 - c0] if raw is not None else get(w0, w1)
+        return _window_positions(cloud_object, buf, w0) + (w1,)
+
+    r0, r1 = c0, c1
+    if start is not None:
+        offs, pos, w1 = window(a, min(b, a + every + 1))
+        k = int(np.searchsorted(pos, start, "left"))
+        r0 = int(offs[k]) if k < len(offs) else w1
+    if end is not None:
+        offs, pos, w1 = window(max(a, b - every), b)
+        k = int(np.searchsorted(pos, end, "right"))
+        r1 = int(offs[k]) if k < len(offs) else w1
+    if r1 <= r0:
+        return c0, c0, (c0, c1), raw
+    return r0, r1, (c0, c1), raw
+
+
+def fetch_region(cloud_object: "CloudObject", chrom, start: Optional[int] = None, end: Optional[int] = None) -> bytes:
+    """The lines of contig ``chrom`` with start <= POS <= end, in file order, each with its terminator.  Coordinates
+    are 1-based and inclusive, as in ``tabix chr:start-end``; None is open on that side.  The test is on POS alone:
+    a record that overlaps the region only through the length of REF or an ``END=`` tag is not returned.  An unknown
+    contig raises KeyError.  One ranged GET fetches the candidate lines, which are cut to the exact ones on the host."""
+    r0, r1, (c0, _), raw = region_range(cloud_object, chrom, start, end, fetch=True)
+    return raw[r0 - c0:r1 - c0]
+
+
+@PartitioningStrategy(dataformat=VCF)
+def partition_contigs_strategy(cloud_object: "CloudObject") -> List[VCFSlice]:
+    """One slice per contig run, in file order: ``get()`` returns the header plus that contig's lines."""
+    names, rows = load_contigs(cloud_object)
+    n = len(rows)
+    return [VCFSlice(range_0=int(r["offset"]), range_1=int(r["end"]), chunk_id=i, num_chunks=n, padding=0,
+                     body=(int(r["offset"]), int(r["end"]))) for i, r in enumerate(rows)]
+
+
+@PartitioningStrategy(dataformat=VCF)
+def partition_regions_strategy(cloud_object: "CloudObject", regions: Sequence[tuple]) -> List[VCFSlice]:
+    """One slice per region ``(chrom, start, end)`` (1-based, inclusive, None open; the test is on POS alone): its
+    body is the tight byte range of the matching lines, empty for a region without any.  Per region at most two
+    sample intervals of lines are read from the object; an open side reads none."""
+    lines = LineIndex.of(cloud_object)
+    out = []
+    for i, (chrom, start, end) in enumerate(regions):
+        r0, r1 = region_range(cloud_object, chrom, start, end, lines=lines)[:2]
+        out.append(VCFSlice(range_0=r0, range_1=r1, chunk_id=i, num_chunks=len(regions), padding=0, body=(r0, r1)))
     return out

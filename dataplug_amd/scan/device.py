@@ -51,6 +51,14 @@ def _retry_capacity(cap: int, launch):
 # the record index (libdpquote.so): what a launch counts, and what the synchronous ``ScanContext.records`` returns
 RecordCounts = namedtuple("RecordCounts", "n n_quotes n_newlines toggles")
 Records = namedtuple("Records", "ends table n_quotes n_newlines toggles n")
+# what ``ScanContext.vcf_positions`` reads back of one part (libdpvpos.so).  Per run, in line order, with line indices
+# local to the launch: ``run_line`` / ``run_pos`` (the run's first line and its POS), ``run_last_line`` / ``run_last``
+# (its last line and that POS), ``names`` and ``run_offset`` (the byte offset of the run's first line).
+# ``first_malformed`` / ``first_unsorted``: the lowest such local index, or None; ``malformed_offset`` /
+# ``unsorted_offset`` those lines' byte offsets and ``first_offset`` that of the launch's line 0.
+VcfPositions = namedtuple("VcfPositions", "n samples run_line run_pos run_last_line run_last names run_offset "
+                                          "n_malformed first_malformed n_unsorted first_unsorted first_pos last_pos "
+                                          "first_offset malformed_offset unsorted_offset")
 _RECORD_FORMS = {"count": None, "u32": np.uint32, "u64": np.uint64, "u16b": np.uint16}
 
 
@@ -133,6 +141,8 @@ class ScanContext:
         self.placements = []                          # per placed buffer: the probe ratios of its candidates
         self._dq = None                               # libdpquote's dq_ctx on this context's stream (records)
         self._dfai = None                             # libdpfai's dfai_ctx on this context's stream (fai_counts)
+        self._dvp = None                              # libdpvpos's dvp_ctx on this context's stream (vcf_positions)
+        self._vp = None                               # the resident lines of the last vcf_lines
 
     # ---------------------------------------------------------------- memory
     def workspace(self, name: str, nbytes: int, placed: bool = False) -> DeviceBuffer:
@@ -593,6 +603,128 @@ class ScanContext:
                                           p(out.ptr), total))
         return lens, self.d2h(np.empty(total, np.uint8), out.ptr)
 
+    # ---------------------------------------------------------------- VCF CHROM / POS (libdpvpos.so)
+    def _vpos_ctx(self):
+        """The context's ``dvp_ctx``, created on first use on the context's current stream."""
+        from . import _vpos
+        if self._dvp is None:
+            h = ctypes.c_void_p()
+            _vpos.check(_vpos.load().dvp_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
+            self._dvp = h
+        return _vpos.load(), self._dvp
+
+    def vpos_geometry(self) -> Tuple[int, int]:
+        """(lines per workgroup of vpos_parse_kernel, of vpos_reduce_kernel) (dvp_geometry)."""
+        from . import _vpos
+        v, h = self._vpos_ctx()
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _vpos.check(v.dvp_geometry(h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
+    def vcf_parse(self, d_buf: int, buf_len: int, buf_base: int, size: int, d_starts: int, n: int) -> None:
+        """The parse launch (vpos_parse_kernel) over ``n`` uint64 line starts at device address ``d_starts``; pos,
+        clen and flags stay in the context's workspace for ``vcf_positions``."""
+        from . import _vpos
+        v, h = self._vpos_ctx()
+        n = int(n)
+        ws = self.workspace("vpos_lines", 7 * n + 64)
+        d_pos, d_clen = ws.ptr, ws.ptr + 4 * n
+        d_clen += d_clen & 1
+        d_flags = d_clen + 2 * n
+        p = ctypes.c_void_p
+        _vpos.check(v.dvp_parse_async(h, p(d_buf), int(buf_len), int(buf_base), int(size), p(d_starts), n, p(d_pos),
+                                      p(d_clen), p(d_flags)))
+        self._vp = dict(d_buf=d_buf, buf_len=int(buf_len), buf_base=int(buf_base), d_starts=d_starts, n=n,
+                        d_pos=d_pos, d_clen=d_clen, d_flags=d_flags)
+
+    def vcf_lines(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, size: int,
+                  first: bool = False, cap: Optional[int] = None) -> int:
+        """The newline launch and the parse launch of one part: the lines that start at p + 1 for a '\\n' at p in
+        object bytes [begin, end), with ``first`` also the line at ``begin`` itself, in front; a start equal to
+        ``size`` is dropped.  Returns the number of lines.  The uint64 starts come from the newline kernel
+        (``delim_ranges_async`` out_mode 1, emit_add 1) and never leave the device."""
+        rg = np.asarray([begin, end], np.uint64)
+        if cap is None:
+            cap = (end - begin) // 32 + 1024
+
+        def launch(cap):
+            ws = self.workspace("vpos_starts", 8 * (cap + 1) + 16)
+            if end > begin:
+                self.delim_ranges_async(d_buf, buf_len, buf_base, rg, 10, 1, 1, 0, ws.ptr + 8, 1, cap)
+                return ws, self.delim_ranges_result(1)[0]
+            return ws, 0
+        ws, n = _retry_capacity(cap, launch)
+        # only a part that reaches the object's end can hold a start equal to ``size`` (the '\n' is the object's last
+        # byte: no line follows it); the others skip the read-back and its synchronisation
+        if n and end >= size and int(self.d2h(np.empty(1, np.uint64), ws.ptr + 8 * n)[0]) >= size:
+            n -= 1
+        d_starts = ws.ptr + 8
+        if first and begin < size:
+            self.h2d(ws.ptr, np.asarray([begin], np.uint64))
+            d_starts, n = ws.ptr, n + 1
+        self.vcf_parse(d_buf, buf_len, buf_base, size, d_starts, n)
+        return n
+
+    def vcf_positions(self, ordinal0: int, every: int, run_cap: int = 1024) -> VcfPositions:
+        """The reduce launch (vpos_reduce_kernel) over the lines of the last ``vcf_lines`` / ``vcf_parse``, line 0 of
+        which has the global ordinal ``ordinal0``, and the names launch over its run starts (include/dpvpos.h).  Only
+        the samples, the runs, the names and the result words are read back."""
+        from . import _vpos
+        v, h = self._vpos_ctx()
+        s = self._vp
+        n = s["n"]
+        k = int(every)
+        ns = -(-(ordinal0 + n) // k) - -(-ordinal0 // k) if k > 0 else 0
+        p = ctypes.c_void_p
+
+        def launch(cap):
+            ws = self.workspace("vpos_out", 4 * ns + 20 * cap + 8 * _vpos.R_WORDS + 64)
+            d_res = ws.ptr
+            d_runs = d_res + 8 * _vpos.R_WORDS
+            d_ends = d_runs + 8 * cap
+            d_rcl = d_ends + 8 * cap
+            d_smp = d_rcl + 4 * cap
+            _vpos.check(v.dvp_reduce_async(h, p(s["d_pos"]), p(s["d_clen"]), p(s["d_flags"]), n, int(ordinal0), k,
+                                           p(d_smp), p(d_runs), p(d_ends), p(d_rcl), cap, p(d_res)))
+            res = self.d2h(np.empty(_vpos.R_WORDS, np.uint64), d_res)
+            if int(res[_vpos.R_RUNS]) > cap:
+                e = DPCapacityError(_lib.DP_ERR_CAPACITY, f"run capacity below {int(res[_vpos.R_RUNS])} entries")
+                e.needed = int(res[_vpos.R_RUNS])
+                raise e
+            m = int(res[_vpos.R_RUNS])
+            out = self.d2h(np.empty(20 * cap + 4 * ns, np.uint8), d_runs)
+            return res, m, out[:8 * m].view(np.uint64), out[8 * cap:8 * cap + 8 * m].view(np.uint64), \
+                out[16 * cap:16 * cap + 4 * m].view(np.uint32), out[20 * cap:].view(np.uint32).copy()
+        res, m, runs, ends, rcl, samples = _retry_capacity(max(1, int(run_cap)), launch)
+        order = np.argsort(runs, kind="stable")
+        runs, rcl, ends = runs[order], rcl[order], np.sort(ends)
+        run_line = (runs >> np.uint64(32)).astype(np.int64)
+        lens = rcl.astype(np.int64)
+        total = int(lens.sum())
+        names, run_offset = [], np.zeros(0, np.uint64)
+        if m:
+            offs = np.zeros(m, np.uint64)
+            np.cumsum(lens[:-1], out=offs[1:], dtype=np.uint64)
+            ws = self.workspace("vpos_names", 20 * m + total + 64)
+            d_off, d_ls, d_lines = ws.ptr, ws.ptr + 8 * m, ws.ptr + 16 * m
+            d_out = d_lines + 4 * m
+            self.h2d(d_off, offs)
+            self.h2d(d_lines, run_line.astype(np.uint32))
+            _vpos.check(v.dvp_names_async(h, p(s["d_buf"]), s["buf_len"], s["buf_base"], p(s["d_starts"]),
+                                          p(s["d_clen"]), n, p(d_lines), p(d_off), m, p(d_out), total, p(d_ls)))
+            run_offset = self.d2h(np.empty(m, np.uint64), d_ls)
+            raw = self.d2h(np.empty(total, np.uint8), d_out).tobytes()
+            names = [raw[int(o):int(o) + int(ln)] for o, ln in zip(offs, lens)]
+        none = np.uint64(_vpos.DVP_NONE)
+        low = lambda w: None if res[w] == none else int(res[w])
+        at = lambda i: None if i is None else int(self.d2h(np.empty(1, np.uint64), s["d_starts"] + 8 * i)[0])
+        fm, fu = low(_vpos.R_MIN_MALFORMED), low(_vpos.R_MIN_UNSORTED)
+        return VcfPositions(n, samples, run_line, (runs & np.uint64(0xFFFFFFFF)).astype(np.int64),
+                            (ends >> np.uint64(32)).astype(np.int64), (ends & np.uint64(0xFFFFFFFF)).astype(np.int64),
+                            names, run_offset, int(res[_vpos.R_MALFORMED]), fm, int(res[_vpos.R_UNSORTED]), fu,
+                            int(res[_vpos.R_FIRST_POS]), int(res[_vpos.R_LAST_POS]), at(0 if n else None), at(fm),
+                            at(fu))
+
     def find_delim(self, d_buf: int, buf_len: int, buf_base: int, start: int, delim: int = 10) -> int:
         """First object offset >= start holding ``delim`` in the buffer, or -1."""
         pos = ctypes.c_int64(-1)
@@ -684,6 +816,10 @@ class ScanContext:
             from . import _fai
             h, self._dfai = self._dfai, None
             _fai.check(_fai.load().dfai_ctx_destroy(h))
+        if self._dvp is not None:
+            from . import _vpos
+            h, self._dvp = self._dvp, None
+            _vpos.check(_vpos.load().dvp_ctx_destroy(h))
         if self.handle:
             for b in list(self._bufs.values()) + list(self._pinned.values()):
                 b.free()

@@ -1009,3 +1009,71 @@ def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: i
     if (nl > 0).any():
         _fai_parts(co, bounds, devs, pass2)
     return names, fai.derive(b, e, nl, cr, first, off, lastoff, names)
+
+
+# ------------------------------------------------------------------------------------------ VCF position index
+def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Optional[int] = None,
+                     part_bytes: int = 2 << 30, halo: int = _HALO0):
+    """The position index of a VCF body (include/dpvpos.h): ``(samples, names, rows, num_lines)`` -- the POS of every
+    ``every``-th line as uint32, and per contig run its name (bytes) and a ``scan.vpos.CONTIG_DTYPE`` row -- or
+    ``scan.vpos.VcfFormatError`` for the first offending line.
+
+    [body_offset, size) is cut with ``line_parts`` and the parts run round-robin on the GPUs.  A part [lo, hi) owns
+    the lines that start behind a '\\n' of its bytes (the first part also the line at ``body_offset``) and is fetched
+    with a look-ahead ``halo`` of at least VPOS_PREFIX_MAX bytes, so a line's prefix is never cut except at the
+    object's end.  A part runs its newline launch and its parse launch at once; its reduce launch needs the number of
+    lines before the part, which the parts chain on the host like ``record_index_object``'s parities (a part that
+    raises releases the parts that wait for it).  ``scan.vpos.merge_parts`` joins the parts."""
+    from . import vpos
+    size = int(co.size)
+    every = int(every)
+    if every < 1 or every & (every - 1):
+        raise ValueError(f"pos_index_every must be a power of two >= 1, not {every}")
+    if halo < 1024:
+        raise ValueError("the halo must hold a line's prefix (VPOS_PREFIX_MAX = 1024 bytes)")
+    if size <= body_offset:
+        return vpos.merge_parts([], size)
+    devs = devices(max_devices, co)
+    bounds = line_parts(body_offset, size, len(devs), part_bytes)
+    counts = [0] * len(bounds)
+    counted = [threading.Event() for _ in bounds]
+    failed = threading.Event()
+    out = [None] * len(bounds)
+
+    def run(k: int):
+        lo, hi = bounds[k]
+        ctx = get_context(devs[k % len(devs)])
+        top = min(size, hi + halo)
+        d = ctx.workspace("input", top - lo + 64, placed=True)
+        dp = d.ptr + (lo & 15)
+        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, top, dp)
+        counts[k] = ctx.vcf_lines(dp, top - lo, lo, lo, hi, size, first=k == 0)
+        counted[k].set()
+        for j in range(k):                               # parts before this one: on this worker done, on others
+            while not counted[j].wait(0.05):             # at least counted before they wait for anything
+                if failed.is_set():
+                    raise RuntimeError("position index: another part failed")
+        out[k] = ctx.vcf_positions(sum(counts[:k]), every)
+
+    by_dev = {}
+    for k in range(len(bounds)):
+        by_dev.setdefault(k % len(devs), []).append(k)
+    errors = []
+
+    def worker(ks):
+        try:
+            for k in ks:
+                run(k)
+        except BaseException as e:
+            errors.append(e)                             # before the event: the first entry is the cause
+            failed.set()
+            raise
+
+    entries = sorted(by_dev)
+    try:
+        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    except BaseException as e:
+        if errors and errors[0] is not e:
+            raise errors[0] from None
+        raise
+    return vpos.merge_parts(out, size)

@@ -235,6 +235,58 @@ def vcf_wide(size: int, seed: int = 0, max_info: int = 1500) -> np.ndarray:
     return out
 
 
+def vcf_sorted(size: int, seed: int = 0, contigs: int = 8, block: int = 4 * 2**20 - 333) -> np.ndarray:
+    """A position-sorted VCF of exactly ``size`` bytes: ``vcf``'s header and row shape, but CHROM is constant within
+    a block of rows (``chr1``, ``chr2``, ... in order, about ``(size - header) / contigs`` bytes each) and POS never
+    decreases within a contig (about one row in eight repeats its neighbour's) and restarts at each contig.
+
+    Each contig is one seeded tile of rows repeated: POS is written as nine digits, the copy's number in the first
+    three (leading zeros) and the tile's own ascending six-digit position behind them, so a copy is the tile's bytes
+    with three digits per row patched.  The last row's last field is padded to the exact size; ends with ``\\n``."""
+    body = size - len(VCF_HEADER)
+    share = body // max(1, contigs)
+    if contigs < 1 or share < 256:
+        raise ValueError(f"vcf_sorted needs at least {len(VCF_HEADER) + 256 * max(1, contigs)} bytes")
+    tile_bytes = max(min(block, share), share // 900 + 1)
+    if tile_bytes > 32 << 20:
+        raise ValueError("vcf_sorted: a contig of this size needs more than 999 copies of a 32 MiB tile")
+    rng = np.random.default_rng(seed)
+    m = tile_bytes // 48 + 8                                  # more rows than the tile can hold (a row has >= 48 bytes)
+    v = rng.integers(0, 1 << 30, (m, 8))
+    top = max(2, min(37, 999_999 // m))
+    rel = np.cumsum(np.where(v[:, 1] % 8 == 0, 0, v[:, 0] % top))
+    gts = [b"0|0", b"0|1", b"1|0", b"1/1", b"./."]
+    tails = [b"%06d\trs%d\t%c\t%c\t%d\tPASS\tNS=3;DP=%d;AF=0.%d\tGT:GQ\t%s:%d\t%s:%d\t%s:%d\n" % (
+        int(rel[j]), int(v[j, 2] % 10**7), b"ACGT"[v[j, 3] % 4], b"ACGT"[v[j, 4] % 4], int(v[j, 5] % 99),
+        int(v[j, 6] % 40), int(v[j, 7] % 1000), gts[v[j, 1] % 5], int(v[j, 2] % 60), gts[v[j, 3] % 5],
+        int(v[j, 4] % 60), gts[v[j, 5] % 5], int(v[j, 6] % 60)) for j in range(m)]
+    tlen = np.fromiter((len(t) for t in tails), np.int64, m)
+    out = np.empty(size, np.uint8)
+    out[:len(VCF_HEADER)] = np.frombuffer(VCF_HEADER, np.uint8)
+    p = len(VCF_HEADER)
+    for c in range(contigs):
+        pre = b"chr%d\t000" % (c + 1)
+        ends = np.cumsum(tlen + len(pre))
+        nrows = max(1, int(np.searchsorted(ends, tile_bytes, "right")))
+        tile = np.frombuffer(b"".join(pre + t for t in tails[:nrows]), np.uint8)
+        digit0 = np.concatenate(([0], ends[:nrows - 1])) + len(pre) - 3          # each row's copy digits in the tile
+        limit = size if c == contigs - 1 else len(VCF_HEADER) + share * (c + 1)
+        k = 0
+        while p < limit:
+            nr = nrows if p + len(tile) <= limit else int(np.searchsorted(ends[:nrows], limit - p, "right"))
+            if nr == 0:
+                break
+            n = int(ends[nr - 1])
+            out[p:p + n] = tile[:n]
+            for d, ch in enumerate(b"%03d" % k):
+                out[p + digit0[:nr] + d] = ch
+            p += n
+            k += 1
+    out[p - 1:size - 1] = ord("x")                            # the last row's last field padded to the exact size
+    out[size - 1] = 10
+    return out
+
+
 def fastq(n_reads: int, seed: int = 0, read_len: int = 100) -> np.ndarray:
     """``n_reads`` 4-line FASTQ reads (inflated stream)."""
     rng = np.random.default_rng(seed)
