@@ -1,4 +1,4 @@
-"""Build libdpscan.so, libdpquote.so, libdpfai.so and libdpvpos.so in-tree for gfx950:  python -m dataplug_amd.build
+"""Build libdpscan.so, libdpquote.so, libdpfai.so, libdpvpos.so and libdpfq.so in-tree for gfx950:  python -m dataplug_amd.build
 
 The scan library is compiled with -save-temps and the ISA guard (dataplug_amd/isa_guard.py) checks that exact
 device assembly: every kernel, no touched in-flight load destination, no scratch segment.  Only a library that
@@ -31,6 +31,9 @@ FAI_REQUIRED = ("fai_count_kernel", "fai_name_kernel")     # the kernels libdpfa
 VPOS_SRC = os.path.join(HERE, "csrc", "dpvpos.hip")        # CHROM / POS parse of a VCF body (include/dpvpos.h)
 VPOS_OUT = os.path.join(HERE, "lib", "libdpvpos.so")
 VPOS_REQUIRED = ("vpos_parse_kernel", "vpos_reduce_kernel", "vpos_name_kernel")   # what libdpvpos.so must contain
+FQ_SRC = os.path.join(HERE, "csrc", "dpfq.hip")            # read lengths and cumulative bases of a FASTQ (include/dpfq.h)
+FQ_OUT = os.path.join(HERE, "lib", "libdpfq.so")
+FQ_REQUIRED = ("fq_read_kernel", "fq_scan_kernel", "fq_sample_kernel")            # what libdpfq.so must contain
 GZ_SRC = os.path.join(HERE, "csrc", "dpgz.c")
 GZ_PAR_SRC = os.path.join(HERE, "csrc", "dpgz_par.c")     # parallel inflate of one gzip stream
 GZ_OUT = os.path.join(HERE, "lib", "libdpgz.so")            # host-side gzip access-point index (zlib)
@@ -107,6 +110,12 @@ def build_vpos(verbose: bool = False) -> str:
     return build(verbose=verbose, out=VPOS_OUT, src=VPOS_SRC, required=VPOS_REQUIRED)
 
 
+def build_fq(verbose: bool = False) -> str:
+    """libdpfq.so: the same hipcc line with -save-temps, the ISA guard on that exact assembly (its own kernel
+    list), installed with its ``.isa.json`` stamp only on "ok"."""
+    return build(verbose=verbose, out=FQ_OUT, src=FQ_SRC, required=FQ_REQUIRED)
+
+
 def build_gz() -> str:
     os.makedirs(os.path.dirname(GZ_OUT), exist_ok=True)
     cc = os.environ.get("CC", "gcc")
@@ -122,3 +131,4 @@ if __name__ == "__main__":
     print(build_quote(verbose="-v" in sys.argv))
     print(build_fai(verbose="-v" in sys.argv))
     print(build_vpos(verbose="-v" in sys.argv))
+    print(build_fq(verbose="-v" in sys.argv))

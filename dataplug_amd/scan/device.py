@@ -59,6 +59,15 @@ Records = namedtuple("Records", "ends table n_quotes n_newlines toggles n")
 VcfPositions = namedtuple("VcfPositions", "n samples run_line run_pos run_last_line run_last names run_offset "
                                           "n_malformed first_malformed n_unsorted first_unsorted first_pos last_pos "
                                           "first_offset malformed_offset unsorted_offset")
+# what ``ScanContext.fastq_reads`` reads back of one part (libdpfq.so).  The part's owned lines are numbered from 0;
+# ``skip`` of them in front belong to a read begun earlier, the device handled the ``n_reads`` reads behind those
+# (global index ``read0`` on) and ``samples`` holds their (offset, bases before it within the launch) pairs.
+# ``edge_lines`` / ``edge_starts``: the local numbers and byte offsets of the lines the device did not handle, and of
+# the first one it did (the terminator of the edge line before it).  ``first_malformed``: the lowest malformed local
+# read or None, with its ``malformed_kind`` (include/dpfq.h) and ``malformed_offset``.  ``closed``: the part reaches
+# the object's end and the object's last byte is a '\n'.
+FastqPart = namedtuple("FastqPart", "n_lines skip read0 n_reads samples bases n_malformed first_malformed "
+                                    "malformed_kind malformed_offset min_len max_len edge_lines edge_starts closed")
 _RECORD_FORMS = {"count": None, "u32": np.uint32, "u64": np.uint64, "u16b": np.uint16}
 
 
@@ -143,6 +152,8 @@ class ScanContext:
         self._dfai = None                             # libdpfai's dfai_ctx on this context's stream (fai_counts)
         self._dvp = None                              # libdpvpos's dvp_ctx on this context's stream (vcf_positions)
         self._vp = None                               # the resident lines of the last vcf_lines
+        self._dfq = None                              # libdpfq's dfq_ctx on this context's stream (fastq_reads)
+        self._fq = None                               # the resident lines of the last fastq_lines
 
     # ---------------------------------------------------------------- memory
     def workspace(self, name: str, nbytes: int, placed: bool = False) -> DeviceBuffer:
@@ -725,6 +736,99 @@ class ScanContext:
                             int(res[_vpos.R_FIRST_POS]), int(res[_vpos.R_LAST_POS]), at(0 if n else None), at(fm),
                             at(fu))
 
+    # ---------------------------------------------------------------- FASTQ reads (libdpfq.so)
+    def _fq_ctx(self):
+        """The context's ``dfq_ctx``, created on first use on the context's current stream."""
+        from . import _fq
+        if self._dfq is None:
+            h = ctypes.c_void_p()
+            _fq.check(_fq.load().dfq_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
+            self._dfq = h
+        return _fq.load(), self._dfq
+
+    def fq_geometry(self) -> Tuple[int, int]:
+        """(reads per workgroup of fq_read_kernel and fq_sample_kernel, lanes of fq_scan_kernel) (dfq_geometry)."""
+        from . import _fq
+        f, h = self._fq_ctx()
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _fq.check(f.dfq_geometry(h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
+    def fastq_lines(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, size: int,
+                    first: bool = False, cap: Optional[int] = None) -> int:
+        """The newline launch of one part, with ``vcf_lines``' ownership: the lines that start at p + 1 for a '\n' at
+        p in object bytes [begin, end), with ``first`` also the line at ``begin`` itself, in front; a start equal to
+        ``size`` is dropped.  Returns the number of lines.  The uint64 starts come from the newline kernel
+        (``delim_ranges_async`` out_mode 1, emit_add 1) and stay on the device for ``fastq_reads``."""
+        rg = np.asarray([begin, end], np.uint64)
+        if cap is None:
+            cap = (end - begin) // 32 + 1024
+
+        def launch(cap):
+            ws = self.workspace("fq_starts", 8 * (cap + 1) + 16)
+            if end > begin:
+                self.delim_ranges_async(d_buf, buf_len, buf_base, rg, 10, 1, 1, 0, ws.ptr + 8, 1, cap)
+                return ws, self.delim_ranges_result(1)[0]
+            return ws, 0
+        ws, n = _retry_capacity(cap, launch)
+        closed = False
+        if n and end >= size and int(self.d2h(np.empty(1, np.uint64), ws.ptr + 8 * n)[0]) >= size:
+            n, closed = n - 1, True
+        d_starts = ws.ptr + 8
+        if first and begin < size:
+            self.h2d(ws.ptr, np.asarray([begin], np.uint64))
+            d_starts, n = ws.ptr, n + 1
+        self._fq = dict(d_buf=d_buf, buf_len=int(buf_len), buf_base=int(buf_base), size=int(size), d_starts=d_starts,
+                        n=n, last=end >= size, closed=closed)
+        return n
+
+    def fastq_reads(self, skip: int, read0: int, every: int) -> FastqPart:
+        """The three launches (fq_read_kernel, fq_scan_kernel, fq_sample_kernel; include/dpfq.h) over the lines of the
+        last ``fastq_lines``: the first ``skip`` lines belong to a read begun before the part, and the reads whose four
+        lines are all complete in the part -- every owned line but the last, whose terminator lies beyond the part's
+        bytes, or every line where the part reaches the object's end -- are the device's, read ``read0`` on.  A part
+        with fewer than 8 lines leaves them all to the host.  Only the samples, the result words and the starts of
+        the edge lines are read back."""
+        from . import _fq
+        s = self._fq
+        n, skip, read0, k = s["n"], int(skip), int(read0), int(every)
+        if k < 1 or k & (k - 1):
+            raise ValueError(f"every must be a power of two >= 1, not {every}")
+        from .fastq import part_plan
+        nr, lines = part_plan(n, skip, s["last"])
+        d_starts = s["d_starts"]
+        u64 = lambda i0, i1: self.d2h(np.empty(max(0, i1 - i0), np.uint64), d_starts + 8 * i0)
+        if nr == 0:
+            return FastqPart(n, skip, read0, 0, np.zeros((0, 2), np.uint64), 0, 0, None, 0, None, None, 0, lines,
+                             u64(0, n), s["closed"])
+        tail = u64(skip + 4 * nr, n)
+        starts = np.concatenate([u64(0, skip + 1), tail])
+        last_end = int(tail[0]) - 1 if len(tail) else s["size"] - (1 if s["closed"] else 0)
+        f, h = self._fq_ctx()
+        g = self.fq_geometry()[0]
+        nb = -(-nr // g)
+        ns = -(-(read0 + nr) // k) - -(-read0 // k)
+        ws = self.workspace("fq_reads", 48 + 16 * ns + 8 * nb + 5 * nr + 64)
+        d_res, d_smp = ws.ptr, ws.ptr + 48
+        d_block = d_smp + 16 * ns
+        d_len = d_block + 8 * nb
+        d_flags = d_len + 4 * nr
+        p = ctypes.c_void_p
+        _fq.check(f.dfq_reads_async(h, p(s["d_buf"]), s["buf_len"], s["buf_base"], s["size"], p(d_starts), skip, nr,
+                                    last_end, p(d_len), p(d_flags), p(d_block), p(d_res)))
+        _fq.check(f.dfq_scan_async(h, p(d_block), nb, p(d_res)))
+        _fq.check(f.dfq_sample_async(h, p(d_starts), skip, p(d_len), p(d_block), nr, read0, k, p(d_smp)))
+        out = self.d2h(np.empty(48 + 16 * ns, np.uint8), d_res)
+        res = out[:8 * _fq.R_WORDS].view(np.uint64)
+        fm = None if int(res[_fq.R_MIN_MALFORMED]) == _fq.DFQ_NONE else int(res[_fq.R_MIN_MALFORMED])
+        kind, off = 0, None
+        if fm is not None:
+            kind = int(self.d2h(np.empty(1, np.uint8), d_flags + fm)[0])
+            off = int(u64(skip + 4 * fm, skip + 4 * fm + 1)[0])
+        return FastqPart(n, skip, read0, nr, out[48:].view(np.uint64).reshape(-1, 2).copy(), int(res[_fq.R_BASES]),
+                         int(res[_fq.R_MALFORMED]), fm, kind, off, int(res[_fq.R_MIN_LEN]), int(res[_fq.R_MAX_LEN]),
+                         lines, starts, s["closed"])
+
     def find_delim(self, d_buf: int, buf_len: int, buf_base: int, start: int, delim: int = 10) -> int:
         """First object offset >= start holding ``delim`` in the buffer, or -1."""
         pos = ctypes.c_int64(-1)
@@ -820,6 +924,10 @@ class ScanContext:
             from . import _vpos
             h, self._dvp = self._dvp, None
             _vpos.check(_vpos.load().dvp_ctx_destroy(h))
+        if self._dfq is not None:
+            from . import _fq
+            h, self._dfq = self._dfq, None
+            _fq.check(_fq.load().dfq_ctx_destroy(h))
         if self.handle:
             for b in list(self._bufs.values()) + list(self._pinned.values()):
                 b.free()

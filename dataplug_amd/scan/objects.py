@@ -1077,3 +1077,88 @@ def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Option
             raise errors[0] from None
         raise
     return vpos.merge_parts(out, size)
+
+
+# ------------------------------------------------------------------------------------------ FASTQ read index
+def reads_index_object(co, every: int = 64, max_devices: Optional[int] = None, part_bytes: int = 2 << 30):
+    """The read index of an uncompressed FASTQ object (include/dpfq.h): a ``scan.fastq.ReadsIndex`` -- the
+    (byte offset, bases before it) of every ``every``-th read plus the closing (size, bases) pair, the number of reads
+    and bases and the shortest and longest read -- or ``scan.fastq.FastqFormatError`` for the first offending read.
+
+    [0, size) is cut with ``line_parts`` and the parts run round-robin on the GPUs.  A part [lo, hi) owns the lines
+    that start behind a '\\n' of its bytes (the first part also the line at 0), as ``pos_index_object``'s parts do, and
+    fetches no halo: an owned line is complete when its terminator lies in the part's bytes, the object's end counting
+    as the last line's.  A part runs its newline launch at once; the three launches over its reads need the number of
+    lines before the part, which the parts chain on the host like ``pos_index_object`` (a part that raises releases
+    the parts that wait for it): with ``b`` lines before it a part skips ``(-b) % 4`` lines and its first read is
+    number ``ceil(b / 4)``.  The device handles the reads whose four lines are all complete in the part; the other
+    owned lines -- at most 3 in front and 4 behind, or all of a part with fewer than 8 -- are edge lines, whose starts
+    ``scan.fastq.merge_parts`` joins across the parts and checks with single-byte ranged GETs: at most four per edge
+    read, one read per boundary of parts with 8 lines or more.  With the default parts that is a handful of requests;
+    with thousands of small parts it is thousands, which run ``GET_THREADS`` at a time, each still a round trip to
+    the store -- small ``part_bytes`` are for tests, not for a remote endpoint.  A part without any line start is
+    legal."""
+    from . import fastq
+    size = int(co.size)
+    every = int(every)
+    if every < 1 or every & (every - 1):
+        raise ValueError(f"reads_index_every must be a power of two >= 1, not {every}")
+    if size == 0:
+        return fastq.empty_index()
+    devs = devices(max_devices, co)
+    bounds = line_parts(0, size, len(devs), part_bytes)
+    counts = [0] * len(bounds)
+    counted = [threading.Event() for _ in bounds]
+    failed = threading.Event()
+    out = [None] * len(bounds)
+
+    def run(k: int, seen: list):
+        lo, hi = bounds[k]
+        ctx = get_context(devs[k % len(devs)])
+        d = ctx.workspace("input", hi - lo + 64, placed=True)
+        dp = d.ptr + (lo & 15)
+        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
+        counts[k] = ctx.fastq_lines(dp, hi - lo, lo, lo, hi, size, first=k == 0)
+        counted[k].set()
+        for j in range(seen[0], k):                      # parts before this one: on this worker done, on others
+            while not counted[j].wait(0.05):             # at least counted before they wait for anything
+                if failed.is_set():
+                    raise RuntimeError("read index: another part failed")
+            seen[1] += counts[j]
+        seen[0] = k                                      # (thousands of small parts: each is waited for once a worker)
+        b = seen[1]
+        out[k] = ctx.fastq_reads((-b) % 4, -(-b // 4), every)
+
+    by_dev = {}
+    for k in range(len(bounds)):
+        by_dev.setdefault(k % len(devs), []).append(k)
+    errors = []
+
+    def worker(ks):
+        try:
+            seen = [0, 0]                                # the parts this worker has seen counted, and their lines
+            for k in ks:
+                run(k, seen)
+        except BaseException as e:
+            errors.append(e)                             # before the event: the first entry is the cause
+            failed.set()
+            raise
+
+    entries = sorted(by_dev)
+    try:
+        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    except BaseException as e:
+        if errors and errors[0] is not e:
+            raise errors[0] from None
+        raise
+
+    def get_byte(q: int) -> int:
+        return co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key, Range=f"bytes={q}-{q}")["Body"].read()[0]
+
+    def get_many(fn, offsets):                           # many small parts: the single-byte GETs side by side
+        if len(offsets) <= 16:
+            return list(map(fn, offsets))
+        with cf.ThreadPoolExecutor(_GET_THREADS) as ex:
+            return list(ex.map(fn, offsets))
+
+    return fastq.merge_parts(out, size, every, get_byte, map_fn=get_many)

@@ -309,6 +309,38 @@ def fastq(n_reads: int, seed: int = 0, read_len: int = 100) -> np.ndarray:
     return out
 
 
+def fastq_long(n_reads: int, seed: int = 0, len_min: int = 100, len_max: int = 100_000, crlf: bool = False) -> np.ndarray:
+    """``n_reads`` 4-line FASTQ reads with long-read lengths: log-uniform in [len_min, len_max], as ONT and PacBio runs
+    spread over orders of magnitude.  ``@read{i} long/1`` headers, a bare ``+``; ``crlf`` ends every line ``\\r\\n``."""
+    rng = np.random.default_rng(seed)
+    eol = 2 if crlf else 1
+    L = np.exp(rng.uniform(np.log(len_min), np.log(len_max + 1), n_reads)).astype(np.int64)
+    L = np.clip(L, len_min, len_max)
+    ids = [b"@read%d long/1" % i for i in range(n_reads)]
+    il = np.fromiter((len(h) for h in ids), np.int64, count=n_reads)
+    rec = il + L + 1 + L + 4 * eol
+    starts = np.concatenate(([0], np.cumsum(rec)[:-1])).astype(np.int64)
+    total = int(rec.sum())
+    out = np.empty(total, np.uint8)
+    if total == 0:
+        return out
+    pick = rng.integers(0, 256, total, dtype=np.uint8)
+    out[:] = _QUAL[pick % len(_QUAL)]                            # the quality bytes; the rest is written over them
+    _scatter_strings(out, starts, np.frombuffer(b"".join(ids), np.uint8), il)
+    seq0 = starts + il + eol
+    seq = np.repeat(seq0 - np.concatenate(([0], np.cumsum(L)[:-1])), L) + np.arange(int(L.sum()), dtype=np.int64)
+    out[seq] = _ACGT[pick[:len(seq)] & 3]
+    plus = seq0 + L + eol
+    out[plus] = ord("+")
+    ends = np.stack([starts + il, seq0 + L, plus + 1, plus + 1 + eol + L])      # each line's first terminator byte
+    if crlf:
+        out[ends] = 13
+        out[ends + 1] = 10
+    else:
+        out[ends] = 10
+    return out
+
+
 def tile_plan(block_len: int, size: int):
     """Copies of a base block that fill ``size`` bytes: list of (dst_offset, length)."""
     plan, off = [], 0
