@@ -7,6 +7,7 @@ bytes / numpy arrays), or caller-owned device memory (e.g. a torch tensor's ``da
 from __future__ import annotations
 
 import ctypes
+import importlib
 import threading
 from collections import namedtuple
 from typing import Iterable, Optional, Sequence, Tuple
@@ -68,6 +69,9 @@ VcfPositions = namedtuple("VcfPositions", "n samples run_line run_pos run_last_l
 # the object's end and the object's last byte is a '\n'.
 FastqPart = namedtuple("FastqPart", "n_lines skip read0 n_reads samples bases n_malformed first_malformed "
                                     "malformed_kind malformed_offset min_len max_len edge_lines edge_starts closed")
+# the libraries that keep a context of their own on a ScanContext's stream, by binding module: the attribute that holds
+# the handle and the prefix of the symbols that create and destroy it (``ScanContext._sub_ctx`` / ``close``)
+_SUB_CTXS = {"_quote": ("_dq", "dq"), "_fai": ("_dfai", "dfai"), "_vpos": ("_dvp", "dvp"), "_fq": ("_dfq", "dfq")}
 _RECORD_FORMS = {"count": None, "u32": np.uint32, "u64": np.uint64, "u16b": np.uint16}
 
 
@@ -445,15 +449,46 @@ class ScanContext:
             return vals, nd, ends
         return _retry_capacity(cap, launch)
 
+    def _line_starts(self, name: str, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, size: int,
+                     first: bool, cap: Optional[int]) -> Tuple[int, int, bool]:
+        """The newline launch of one part (``vcf_lines`` / ``fastq_lines``), the uint64 starts left in workspace
+        ``name``: (their device address, their number, whether a start equal to ``size`` was dropped)."""
+        rg = np.asarray([begin, end], np.uint64)
+        if cap is None:
+            cap = (end - begin) // 32 + 1024
+
+        def launch(cap):
+            ws = self.workspace(name, 8 * (cap + 1) + 16)
+            if end > begin:
+                self.delim_ranges_async(d_buf, buf_len, buf_base, rg, 10, 1, 1, 0, ws.ptr + 8, 1, cap)
+                return ws, self.delim_ranges_result(1)[0]
+            return ws, 0
+        ws, n = _retry_capacity(cap, launch)
+        # only a part that reaches the object's end can hold a start equal to ``size`` (the '\n' is the object's last
+        # byte: no line follows it); the others skip the read-back and its synchronisation
+        dropped = bool(n and end >= size and int(self.d2h(np.empty(1, np.uint64), ws.ptr + 8 * n)[0]) >= size)
+        n -= dropped
+        if first and begin < size:
+            self.h2d(ws.ptr, np.asarray([begin], np.uint64))
+            return ws.ptr, n + 1, dropped
+        return ws.ptr + 8, n, dropped
+
+    # ---------------------------------------------------------------- the other libraries' contexts
+    def _sub_ctx(self, name: str):
+        """(library, handle) of binding module ``name`` (``_SUB_CTXS``): its context on this one's device, created on
+        first use on this context's current stream."""
+        attr, prefix = _SUB_CTXS[name]
+        mod = importlib.import_module("." + name, __package__)
+        if getattr(self, attr) is None:
+            h = ctypes.c_void_p()
+            create = getattr(mod.load(), prefix + "_ctx_create")
+            mod.check(create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
+            setattr(self, attr, h)
+        return mod.load(), getattr(self, attr)
+
     # ---------------------------------------------------------------- quote-aware record ends (libdpquote.so)
     def _quote_ctx(self):
-        """The context's ``dq_ctx``, created on first use on the context's current stream."""
-        from . import _quote
-        if self._dq is None:
-            h = ctypes.c_void_p()
-            _quote.check(_quote.load().dq_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
-            self._dq = h
-        return _quote.load(), self._dq
+        return self._sub_ctx("_quote")
 
     def quote_geometry(self) -> Tuple[int, int]:
         """(tile bytes, workgroups of the persistent grid) of the record-end kernel (dq_geometry)."""
@@ -540,13 +575,7 @@ class ScanContext:
 
     # ---------------------------------------------------------------- FASTA .fai counts (libdpfai.so)
     def _fai_ctx(self):
-        """The context's ``dfai_ctx``, created on first use on the context's current stream."""
-        from . import _fai
-        if self._dfai is None:
-            h = ctypes.c_void_p()
-            _fai.check(_fai.load().dfai_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
-            self._dfai = h
-        return _fai.load(), self._dfai
+        return self._sub_ctx("_fai")
 
     def fai_geometry(self) -> Tuple[int, int, int]:
         """(R, the bytes of the range a wave takes at a time; K, the per-wave segment slots; the waves of the grid)
@@ -616,13 +645,7 @@ class ScanContext:
 
     # ---------------------------------------------------------------- VCF CHROM / POS (libdpvpos.so)
     def _vpos_ctx(self):
-        """The context's ``dvp_ctx``, created on first use on the context's current stream."""
-        from . import _vpos
-        if self._dvp is None:
-            h = ctypes.c_void_p()
-            _vpos.check(_vpos.load().dvp_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
-            self._dvp = h
-        return _vpos.load(), self._dvp
+        return self._sub_ctx("_vpos")
 
     def vpos_geometry(self) -> Tuple[int, int]:
         """(lines per workgroup of vpos_parse_kernel, of vpos_reduce_kernel) (dvp_geometry)."""
@@ -654,25 +677,7 @@ class ScanContext:
         object bytes [begin, end), with ``first`` also the line at ``begin`` itself, in front; a start equal to
         ``size`` is dropped.  Returns the number of lines.  The uint64 starts come from the newline kernel
         (``delim_ranges_async`` out_mode 1, emit_add 1) and never leave the device."""
-        rg = np.asarray([begin, end], np.uint64)
-        if cap is None:
-            cap = (end - begin) // 32 + 1024
-
-        def launch(cap):
-            ws = self.workspace("vpos_starts", 8 * (cap + 1) + 16)
-            if end > begin:
-                self.delim_ranges_async(d_buf, buf_len, buf_base, rg, 10, 1, 1, 0, ws.ptr + 8, 1, cap)
-                return ws, self.delim_ranges_result(1)[0]
-            return ws, 0
-        ws, n = _retry_capacity(cap, launch)
-        # only a part that reaches the object's end can hold a start equal to ``size`` (the '\n' is the object's last
-        # byte: no line follows it); the others skip the read-back and its synchronisation
-        if n and end >= size and int(self.d2h(np.empty(1, np.uint64), ws.ptr + 8 * n)[0]) >= size:
-            n -= 1
-        d_starts = ws.ptr + 8
-        if first and begin < size:
-            self.h2d(ws.ptr, np.asarray([begin], np.uint64))
-            d_starts, n = ws.ptr, n + 1
+        d_starts, n, _ = self._line_starts("vpos_starts", d_buf, buf_len, buf_base, begin, end, size, first, cap)
         self.vcf_parse(d_buf, buf_len, buf_base, size, d_starts, n)
         return n
 
@@ -738,13 +743,7 @@ class ScanContext:
 
     # ---------------------------------------------------------------- FASTQ reads (libdpfq.so)
     def _fq_ctx(self):
-        """The context's ``dfq_ctx``, created on first use on the context's current stream."""
-        from . import _fq
-        if self._dfq is None:
-            h = ctypes.c_void_p()
-            _fq.check(_fq.load().dfq_ctx_create(self.device, ctypes.c_void_p(self.stream), ctypes.byref(h)))
-            self._dfq = h
-        return _fq.load(), self._dfq
+        return self._sub_ctx("_fq")
 
     def fq_geometry(self) -> Tuple[int, int]:
         """(reads per workgroup of fq_read_kernel and fq_sample_kernel, lanes of fq_scan_kernel) (dfq_geometry)."""
@@ -760,24 +759,7 @@ class ScanContext:
         p in object bytes [begin, end), with ``first`` also the line at ``begin`` itself, in front; a start equal to
         ``size`` is dropped.  Returns the number of lines.  The uint64 starts come from the newline kernel
         (``delim_ranges_async`` out_mode 1, emit_add 1) and stay on the device for ``fastq_reads``."""
-        rg = np.asarray([begin, end], np.uint64)
-        if cap is None:
-            cap = (end - begin) // 32 + 1024
-
-        def launch(cap):
-            ws = self.workspace("fq_starts", 8 * (cap + 1) + 16)
-            if end > begin:
-                self.delim_ranges_async(d_buf, buf_len, buf_base, rg, 10, 1, 1, 0, ws.ptr + 8, 1, cap)
-                return ws, self.delim_ranges_result(1)[0]
-            return ws, 0
-        ws, n = _retry_capacity(cap, launch)
-        closed = False
-        if n and end >= size and int(self.d2h(np.empty(1, np.uint64), ws.ptr + 8 * n)[0]) >= size:
-            n, closed = n - 1, True
-        d_starts = ws.ptr + 8
-        if first and begin < size:
-            self.h2d(ws.ptr, np.asarray([begin], np.uint64))
-            d_starts, n = ws.ptr, n + 1
+        d_starts, n, closed = self._line_starts("fq_starts", d_buf, buf_len, buf_base, begin, end, size, first, cap)
         self._fq = dict(d_buf=d_buf, buf_len=int(buf_len), buf_base=int(buf_base), size=int(size), d_starts=d_starts,
                         n=n, last=end >= size, closed=closed)
         return n
@@ -912,22 +894,12 @@ class ScanContext:
         if self._get_pool is not None:
             self._get_pool.shutdown(wait=True)
             self._get_pool = None
-        if self._dq is not None:
-            from . import _quote
-            h, self._dq = self._dq, None
-            _quote.check(_quote.load().dq_ctx_destroy(h))
-        if self._dfai is not None:
-            from . import _fai
-            h, self._dfai = self._dfai, None
-            _fai.check(_fai.load().dfai_ctx_destroy(h))
-        if self._dvp is not None:
-            from . import _vpos
-            h, self._dvp = self._dvp, None
-            _vpos.check(_vpos.load().dvp_ctx_destroy(h))
-        if self._dfq is not None:
-            from . import _fq
-            h, self._dfq = self._dfq, None
-            _fq.check(_fq.load().dfq_ctx_destroy(h))
+        for name, (attr, prefix) in _SUB_CTXS.items():
+            h = getattr(self, attr, None)                 # (a context built without some of them closes too)
+            if h is not None:
+                mod = importlib.import_module("." + name, __package__)
+                setattr(self, attr, None)
+                mod.check(getattr(mod.load(), prefix + "_ctx_destroy")(h))
         if self.handle:
             for b in list(self._bufs.values()) + list(self._pinned.values()):
                 b.free()

@@ -191,6 +191,79 @@ def run_on_devices(devs: Sequence[int], jobs: Sequence) -> list:
     return [f.result() for f in futs]
 
 
+class PartChain:
+    """One integer per part of a part-wise build (a count of quotes or of lines), summed along the parts on the host:
+    ``publish(k, value)`` hands in part k's, ``before(k)`` is the sum of parts 0 .. k - 1, waited for.  One call's.
+
+    Invariant: a part publishes before it waits for anything.  The parts of one device entry run in order on one
+    worker, so a part that waited first would keep the worker from the entry's next part, whose value a part on
+    another worker waits for in turn: with it, whatever ``before(k)`` waits for is a part that is done, or counted on
+    another worker, or failed -- and ``run_parts`` sets ``failed`` for that one, which the 50 ms poll notices."""
+
+    def __init__(self, n_parts: int, label: str):
+        self.label = label
+        self.values = [0] * n_parts
+        self.published = [threading.Event() for _ in range(n_parts)]
+        self.failed = threading.Event()
+        self.errors = []                                 # run_parts': the first entry is the cause
+        self._seen = threading.local()                   # per worker: the parts it has seen published, and their sum
+
+    def publish(self, k: int, value: int) -> None:
+        self.values[k] = value
+        self.published[k].set()
+
+    def before(self, k: int) -> int:
+        seen = self._seen.__dict__.setdefault("cursor", [0, 0])
+        if k < seen[0]:
+            seen[:] = [0, 0]
+        for j in range(seen[0], k):                      # (thousands of small parts: each is waited for once a worker)
+            while not self.published[j].wait(0.05):
+                if self.failed.is_set():
+                    raise RuntimeError(f"{self.label}: another part failed")
+            seen[1] += self.values[j]
+        seen[0] = k
+        return seen[1]
+
+
+def run_parts(devs: Sequence[int], n_parts: int, job, chain: Optional[PartChain] = None) -> None:
+    """Run ``job(k, entry_parts)`` for every part: part k on device entry k mod len(devs), the parts of one entry in
+    order on that entry's persistent worker (``run_on_devices``: the same thread and context in every call, the
+    calling thread for a single entry).  ``entry_parts``: the parts the entry holds.  With a ``chain`` a part that
+    raises releases the parts that wait in ``chain.before``, and the caller gets that failure itself, not the error
+    of a released waiter whose worker happens to come first."""
+    by_dev = {}
+    for k in range(n_parts):
+        by_dev.setdefault(k % len(devs), []).append(k)
+
+    def worker(ks):
+        try:
+            for k in ks:
+                job(k, len(ks))
+        except BaseException as e:
+            if chain is not None:
+                chain.errors.append(e)                   # before the event: the first entry is the cause, the parts
+                chain.failed.set()                       # it releases add their own error behind it
+            raise
+
+    entries = sorted(by_dev)
+    try:
+        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    except BaseException as e:
+        if chain is not None and chain.errors and chain.errors[0] is not e:
+            raise chain.errors[0] from None
+        raise
+
+
+def _resident(ctx: ScanContext, co, lo: int, top: int, fetch: bool = True) -> int:
+    """The device address of object byte ``lo`` in ``ctx``'s input buffer, sized for [lo, top) and, with ``fetch``,
+    filled with those bytes on the context stream.  The address is congruent to ``lo`` mod 16: the grid of the
+    blocked kernels (out_mode 3 / 4, the u16b record form) counts in object offsets and loads 16 aligned bytes."""
+    dp = ctx.workspace("input", top - lo + 64, placed=True).ptr + (lo & 15)
+    if fetch:
+        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, top, dp)
+    return dp
+
+
 # ------------------------------------------------------------------------------------------ FASTA
 @dataclass(frozen=True)
 class FastaGroup:
@@ -532,9 +605,7 @@ def line_parts(begin: int, end: int, n_devices: int, part_bytes: int = 16 << 30)
 def _delim_group(dev: int, co, lo: int, hi: int, delim: int, every_k: int, emit_add: int, fmt: str = "u64"):
     ctx = get_context(dev)
     n = hi - lo
-    d = ctx.workspace("input", n + 64, placed=True)
-    dp = d.ptr + (lo & 15)                # object offset and device address congruent mod 16 (out_mode 3 grid)
-    fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
+    dp = _resident(ctx, co, lo, hi)
     if fmt == "u64":
         return ctx.delim_index(dp, n, lo, lo, hi, delim=delim, every_k=every_k, emit_add=emit_add, u64=True)
     if fmt == "u32p":
@@ -572,23 +643,14 @@ def line_index_object(co, begin: int = 0, end: Optional[int] = None, delim: int 
     devs = devices(max_devices, co)
     bounds = line_parts(begin, end, len(devs), part_bytes)
 
-    def run(k: int):
-        lo, hi = bounds[k]
-        r = _delim_group(devs[k % len(devs)], co, lo, hi, delim, 1, 0, fmt=fmt)
-        return r[0] if fmt == "u64" else r
-
-    # parts of one device entry run in order on that entry's persistent worker (run_on_devices)
-    by_dev = {}
-    for k in range(len(bounds)):
-        by_dev.setdefault(k % len(devs), []).append(k)
     out = [None] * len(bounds)
 
-    def worker(ks):
-        for k in ks:
-            out[k] = run(k)
+    def run(k: int, _):
+        lo, hi = bounds[k]
+        r = _delim_group(devs[k % len(devs)], co, lo, hi, delim, 1, 0, fmt=fmt)
+        out[k] = r[0] if fmt == "u64" else r
 
-    entries = sorted(by_dev)
-    run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
+    run_parts(devs, len(bounds), run)
     if fmt == "u64":
         return out[0] if len(out) == 1 else np.concatenate(out)
     low = out[0][0] if len(out) == 1 else np.concatenate([o[0] for o in out])
@@ -648,7 +710,7 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
     The parts come from ``line_parts`` and run round-robin on the GPUs like a newline index.  A part does not know
     whether it starts inside a quoted field, so it runs two launches on its resident bytes: a count-only one that
     yields its number of quote bytes, and -- once the counts of every part before it are in, chained on the host
-    into the part's incoming state -- the emitting one.  The second read is of HBM, not of the storage.
+    (``PartChain``) into the part's incoming state -- the emitting one.  The second read is of HBM, not of the storage.
 
     ``escape``: the byte that makes the next byte literal (include/dpquote.h; ``escape_scope`` "all" or "quoted"), for
     objects that write a quote inside a field as ``\\"``.  Whether a part's first byte is escaped is read from the
@@ -667,57 +729,25 @@ def record_index_object(co, begin: int = 0, end: Optional[int] = None, quote: in
             BlockedOffsets(np.zeros(0, np.uint16), np.zeros(1, np.uint64), begin >> 16)
     devs = devices(max_devices, co)
     bounds = line_parts(begin, end, len(devs), part_bytes)
-    quotes = [0] * len(bounds)
-    counted = [threading.Event() for _ in bounds]
-    failed = threading.Event()
+    chain = PartChain(len(bounds), "record index")
     out = [None] * len(bounds)
 
-    def run(k: int):
+    def run(k: int, _):
         lo, hi = bounds[k]
         ctx = get_context(devs[k % len(devs)])
         n = hi - lo
-        d = ctx.workspace("input", n + 64, placed=True)
-        dp = d.ptr + (lo & 15)
-        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
+        dp = _resident(ctx, co, lo, hi)
         ec = escape_carry_at(co, begin, lo, escape) if k and escape is not None else 0
         esc = dict(escape=escape, esc_carry=ec, scope=escape_scope)
         counts = ctx.records(dp, n, lo, lo, hi, quote=quote, carry=0, form="count", **esc)
-        n_rec, quotes[k] = counts.n, counts.toggles      # a plain launch toggles at every quote byte
-        counted[k].set()
-        for j in range(k):                               # parts before this one: on this worker done, on others
-            while not counted[j].wait(0.05):             # at least counted before they wait for anything
-                if failed.is_set():
-                    raise RuntimeError("record index: another part failed")
-        carry = sum(quotes[:k]) & 1
+        chain.publish(k, counts.toggles)                 # a plain launch toggles at every quote byte
+        carry = chain.before(k) & 1
         # the count under carry 0 bounds nothing under carry 1: size the output by the newlines only on a retry
-        cap = max(n_rec, 1) if carry == 0 else None
-        # dp is congruent to lo mod 16: the blocked form's grid
+        cap = max(counts.n, 1) if carry == 0 else None
         r = ctx.records(dp, n, lo, lo, hi, quote=quote, carry=carry, form=fmt, cap=cap, **esc)
         out[k] = (r.ends, r.table) if fmt == "u16b" else r.ends
 
-    by_dev = {}
-    for k in range(len(bounds)):
-        by_dev.setdefault(k % len(devs), []).append(k)
-
-    errors = []
-
-    def worker(ks):
-        try:
-            for k in ks:
-                run(k)
-        except BaseException as e:
-            errors.append(e)                             # before the event: the first entry is the cause, the parts
-            failed.set()                                 # it releases add their "another part failed" behind it
-            raise
-
-    entries = sorted(by_dev)
-    try:
-        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
-    except BaseException as e:
-        # the caller gets the failure itself, not the error of a released waiter whose worker happens to come first
-        if errors and errors[0] is not e:
-            raise errors[0] from None
-        raise
+    run_parts(devs, len(bounds), run, chain)
     if fmt == "u64":
         return out[0] if len(out) == 1 else np.concatenate(out)
     if len(out) == 1:                                    # one part: [begin, end) itself, its table as it is
@@ -878,8 +908,7 @@ def _delim_piece_run(dev: int, co, jobs, delim: int, fmt: str, stop: threading.E
                 ctx = ctxs[i % _PIECE_CTXS]
                 gets = nxt if nxt is not None else queue_gets(i)
                 nxt = queue_gets(i + 1) if i + 1 < len(jobs) else None
-                d = ctx.workspace("input", hi - lo + 64, placed=True)
-                dp = d.ptr + (lo & 15)               # object offset and device address congruent mod 16
+                dp = _resident(ctx, co, lo, hi, fetch=False)
                 land_gets(ctx, gets, dp)
                 reads.append(rb.submit(collect, launch(ctx, lo, hi, dp), fut))
             cf.wait(reads)
@@ -907,23 +936,6 @@ def record_index_bytes(data, delim: int = 10, every_k: int = 1, emit_add: int = 
 
 
 # ------------------------------------------------------------------------------------------ FASTA .fai
-def _fai_parts(co, bounds, devs, job):
-    """Run ``job(ctx, k, refetch)`` for every part: part k on device entry k mod len(devs), the parts of one entry in
-    order on that entry's persistent worker (the same thread and context in every call).  ``refetch`` tells a job
-    whether its entry holds more than one part, i.e. whether the entry's resident bytes are another part's."""
-    by_dev = {}
-    for k in range(len(bounds)):
-        by_dev.setdefault(k % len(devs), []).append(k)
-
-    def worker(entry):
-        ctx = get_context(devs[entry])
-        for k in by_dev[entry]:
-            job(ctx, k, len(by_dev[entry]) > 1)
-
-    entries = sorted(by_dev)
-    run_on_devices([devs[en] for en in entries], [partial(worker, en) for en in entries])
-
-
 def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: int = 8 << 30, halo: int = _HALO0):
     """The faidx-compatible index of a FASTA object from its stored header ``pairs`` [(start, end), ...]
     (include/dpfai.h): ``(names, rows)``, the names as a list of bytes and ``rows`` a ``scan.fai.FAI_DTYPE`` array
@@ -959,18 +971,14 @@ def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: i
         keep = np.flatnonzero(phi > plo)
         return i0 + keep, plo[keep], phi[keep]
 
-    def resident(ctx, k, fetch):
+    def resident(k, fetch):
         lo, hi = bounds[k]
-        top = min(size, hi + halo)
-        d = ctx.workspace("input", top - lo + 64, placed=True)
-        dp = d.ptr + (lo & 15)
-        if fetch:
-            fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, top, dp)
-        return dp, top
+        ctx, top = get_context(devs[k % len(devs)]), min(size, hi + halo)
+        return ctx, _resident(ctx, co, lo, top, fetch), top
 
-    def pass1(ctx, k, _):
+    def pass1(k, _):
         lo, hi = bounds[k]
-        dp, top = resident(ctx, k, True)
+        ctx, dp, top = resident(k, True)
         idx, plo, phi = clip(k)
         r = ctx.fai_counts(dp, top - lo, lo, plo, phi, b[idx])
         j0, j1 = int(np.searchsorted(starts, lo, "left")), int(np.searchsorted(starts, hi, "left"))
@@ -986,7 +994,7 @@ def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: i
             for j in np.flatnonzero((starts[j0:j1] + np.uint64(1) + lens == cut) & (cut < hends[j0:j1])):
                 long_names[j0 + int(j)] = None
 
-    _fai_parts(co, bounds, devs, pass1)
+    run_parts(devs, len(bounds), pass1)
     names = fai.split_names(name_lens, np.concatenate(name_bytes) if name_bytes else np.zeros(0, np.uint8))
     for j in long_names:
         raw = co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key,
@@ -997,9 +1005,9 @@ def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: i
     width = fai.line_widths(b, e, nl, first)
     w32 = np.minimum(width, np.uint64(0xFFFFFFFF)).astype(np.uint32)     # (a wider one is an error anyway)
 
-    def pass2(ctx, k, refetch):
+    def pass2(k, entry_parts):
         lo, hi = bounds[k]
-        dp, top = resident(ctx, k, refetch)
+        ctx, dp, top = resident(k, entry_parts > 1)      # several parts: the entry's resident bytes are another part's
         idx, plo, phi = clip(k)
         r = ctx.fai_counts(dp, top - lo, lo, plo, phi, b[idx], width=w32[idx])
         with lock:
@@ -1007,7 +1015,7 @@ def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: i
             lastoff[idx] = np.maximum(lastoff[idx], r[1])
 
     if (nl > 0).any():
-        _fai_parts(co, bounds, devs, pass2)
+        run_parts(devs, len(bounds), pass2)
     return names, fai.derive(b, e, nl, cr, first, off, lastoff, names)
 
 
@@ -1022,8 +1030,8 @@ def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Option
     the lines that start behind a '\\n' of its bytes (the first part also the line at ``body_offset``) and is fetched
     with a look-ahead ``halo`` of at least VPOS_PREFIX_MAX bytes, so a line's prefix is never cut except at the
     object's end.  A part runs its newline launch and its parse launch at once; its reduce launch needs the number of
-    lines before the part, which the parts chain on the host like ``record_index_object``'s parities (a part that
-    raises releases the parts that wait for it).  ``scan.vpos.merge_parts`` joins the parts."""
+    lines before the part, which the parts chain on the host (``PartChain``, like ``record_index_object``'s
+    parities).  ``scan.vpos.merge_parts`` joins the parts."""
     from . import vpos
     size = int(co.size)
     every = int(every)
@@ -1035,47 +1043,18 @@ def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Option
         return vpos.merge_parts([], size)
     devs = devices(max_devices, co)
     bounds = line_parts(body_offset, size, len(devs), part_bytes)
-    counts = [0] * len(bounds)
-    counted = [threading.Event() for _ in bounds]
-    failed = threading.Event()
+    chain = PartChain(len(bounds), "position index")
     out = [None] * len(bounds)
 
-    def run(k: int):
+    def run(k: int, _):
         lo, hi = bounds[k]
         ctx = get_context(devs[k % len(devs)])
         top = min(size, hi + halo)
-        d = ctx.workspace("input", top - lo + 64, placed=True)
-        dp = d.ptr + (lo & 15)
-        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, top, dp)
-        counts[k] = ctx.vcf_lines(dp, top - lo, lo, lo, hi, size, first=k == 0)
-        counted[k].set()
-        for j in range(k):                               # parts before this one: on this worker done, on others
-            while not counted[j].wait(0.05):             # at least counted before they wait for anything
-                if failed.is_set():
-                    raise RuntimeError("position index: another part failed")
-        out[k] = ctx.vcf_positions(sum(counts[:k]), every)
+        dp = _resident(ctx, co, lo, top)
+        chain.publish(k, ctx.vcf_lines(dp, top - lo, lo, lo, hi, size, first=k == 0))
+        out[k] = ctx.vcf_positions(chain.before(k), every)
 
-    by_dev = {}
-    for k in range(len(bounds)):
-        by_dev.setdefault(k % len(devs), []).append(k)
-    errors = []
-
-    def worker(ks):
-        try:
-            for k in ks:
-                run(k)
-        except BaseException as e:
-            errors.append(e)                             # before the event: the first entry is the cause
-            failed.set()
-            raise
-
-    entries = sorted(by_dev)
-    try:
-        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
-    except BaseException as e:
-        if errors and errors[0] is not e:
-            raise errors[0] from None
-        raise
+    run_parts(devs, len(bounds), run, chain)
     return vpos.merge_parts(out, size)
 
 
@@ -1089,9 +1068,8 @@ def reads_index_object(co, every: int = 64, max_devices: Optional[int] = None, p
     that start behind a '\\n' of its bytes (the first part also the line at 0), as ``pos_index_object``'s parts do, and
     fetches no halo: an owned line is complete when its terminator lies in the part's bytes, the object's end counting
     as the last line's.  A part runs its newline launch at once; the three launches over its reads need the number of
-    lines before the part, which the parts chain on the host like ``pos_index_object`` (a part that raises releases
-    the parts that wait for it): with ``b`` lines before it a part skips ``(-b) % 4`` lines and its first read is
-    number ``ceil(b / 4)``.  The device handles the reads whose four lines are all complete in the part; the other
+    lines before the part, which the parts chain on the host (``PartChain``): with ``b`` lines before it a part skips
+    ``(-b) % 4`` lines and its first read is number ``ceil(b / 4)``.  The device handles the reads whose four lines are all complete in the part; the other
     owned lines -- at most 3 in front and 4 behind, or all of a part with fewer than 8 -- are edge lines, whose starts
     ``scan.fastq.merge_parts`` joins across the parts and checks with single-byte ranged GETs: at most four per edge
     read, one read per boundary of parts with 8 lines or more.  With the default parts that is a handful of requests;
@@ -1107,50 +1085,18 @@ def reads_index_object(co, every: int = 64, max_devices: Optional[int] = None, p
         return fastq.empty_index()
     devs = devices(max_devices, co)
     bounds = line_parts(0, size, len(devs), part_bytes)
-    counts = [0] * len(bounds)
-    counted = [threading.Event() for _ in bounds]
-    failed = threading.Event()
+    chain = PartChain(len(bounds), "read index")
     out = [None] * len(bounds)
 
-    def run(k: int, seen: list):
+    def run(k: int, _):
         lo, hi = bounds[k]
         ctx = get_context(devs[k % len(devs)])
-        d = ctx.workspace("input", hi - lo + 64, placed=True)
-        dp = d.ptr + (lo & 15)
-        fetch_to_device(ctx, co.storage, co.path.bucket, co.path.key, lo, hi, dp)
-        counts[k] = ctx.fastq_lines(dp, hi - lo, lo, lo, hi, size, first=k == 0)
-        counted[k].set()
-        for j in range(seen[0], k):                      # parts before this one: on this worker done, on others
-            while not counted[j].wait(0.05):             # at least counted before they wait for anything
-                if failed.is_set():
-                    raise RuntimeError("read index: another part failed")
-            seen[1] += counts[j]
-        seen[0] = k                                      # (thousands of small parts: each is waited for once a worker)
-        b = seen[1]
+        dp = _resident(ctx, co, lo, hi)
+        chain.publish(k, ctx.fastq_lines(dp, hi - lo, lo, lo, hi, size, first=k == 0))
+        b = chain.before(k)
         out[k] = ctx.fastq_reads((-b) % 4, -(-b // 4), every)
 
-    by_dev = {}
-    for k in range(len(bounds)):
-        by_dev.setdefault(k % len(devs), []).append(k)
-    errors = []
-
-    def worker(ks):
-        try:
-            seen = [0, 0]                                # the parts this worker has seen counted, and their lines
-            for k in ks:
-                run(k, seen)
-        except BaseException as e:
-            errors.append(e)                             # before the event: the first entry is the cause
-            failed.set()
-            raise
-
-    entries = sorted(by_dev)
-    try:
-        run_on_devices([devs[e] for e in entries], [partial(worker, by_dev[e]) for e in entries])
-    except BaseException as e:
-        if errors and errors[0] is not e:
-            raise errors[0] from None
-        raise
+    run_parts(devs, len(bounds), run, chain)
 
     def get_byte(q: int) -> int:
         return co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key, Range=f"bytes={q}-{q}")["Body"].read()[0]
