@@ -936,6 +936,16 @@ def record_index_bytes(data, delim: int = 10, every_k: int = 1, emit_add: int = 
 
 
 # ------------------------------------------------------------------------------------------ FASTA .fai
+def clip_bodies(b: np.ndarray, e: np.ndarray, lo: int, hi: int):
+    """The bodies [b_i, e_i) (ascending, ``scan.fai.bodies``) that hold a byte of part [lo, hi), clipped to it:
+    (their indices, the clipped starts, the clipped ends), uint64 -- the segments of the part's ``fai_counts``, whose
+    ``origin`` stays the unclipped ``b[indices]``."""
+    i0, i1 = int(np.searchsorted(e, lo, "right")), int(np.searchsorted(b, hi, "left"))
+    plo, phi = np.clip(b[i0:i1], lo, hi).astype(np.uint64), np.clip(e[i0:i1], lo, hi).astype(np.uint64)
+    keep = np.flatnonzero(phi > plo)
+    return i0 + keep, plo[keep], phi[keep]
+
+
 def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: int = 8 << 30, halo: int = _HALO0):
     """The faidx-compatible index of a FASTA object from its stored header ``pairs`` [(start, end), ...]
     (include/dpfai.h): ``(names, rows)``, the names as a list of bytes and ``rows`` a ``scan.fai.FAI_DTYPE`` array
@@ -965,11 +975,7 @@ def fai_index_object(co, pairs, max_devices: Optional[int] = None, part_bytes: i
     lock = threading.Lock()
 
     def clip(k):
-        lo, hi = bounds[k]
-        i0, i1 = int(np.searchsorted(e, lo, "right")), int(np.searchsorted(b, hi, "left"))
-        plo, phi = np.clip(b[i0:i1], lo, hi).astype(np.uint64), np.clip(e[i0:i1], lo, hi).astype(np.uint64)
-        keep = np.flatnonzero(phi > plo)
-        return i0 + keep, plo[keep], phi[keep]
+        return clip_bodies(b, e, *bounds[k])
 
     def resident(k, fetch):
         lo, hi = bounds[k]

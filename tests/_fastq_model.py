@@ -107,15 +107,26 @@ class ModelDevices:
         ctx.mem[d_ptr - ctx.BASE:d_ptr - ctx.BASE + hi - lo] = np.frombuffer(raw, np.uint8)
 
 
-def parts_by_cuts(data: bytes, cuts, every: int):
-    """The merge's input for parts cut at ``cuts``: each part sees its own bytes only."""
+def model_part(data: bytes):
+    """The ``make_part`` of ``parts_by_cuts`` over the model: a fresh context that holds the part's buffer only."""
+    def make_part(k, lo, hi, top):
+        ctx = ModelContext()
+        ctx.mem = np.frombuffer(data[lo:top], np.uint8)
+        return ctx, ctx.BASE
+    return make_part
+
+
+def parts_by_cuts(data: bytes, cuts, every: int, make_part=None):
+    """The merge's input for parts cut at ``cuts``: each part sees its own bytes only (no halo: top = hi).
+    ``make_part(k, lo, hi, top)`` gives ``(ctx, d_buf)``, the context that runs the part and the device address of
+    object byte ``lo`` in it: the model's by default, or a real ``ScanContext`` with the bytes uploaded."""
     size = len(data)
     edges = [0] + sorted(cuts) + [size]
     parts, before = [], 0
+    make_part = make_part or model_part(data)
     for k, (lo, hi) in enumerate(zip(edges[:-1], edges[1:])):
-        ctx = ModelContext()
-        ctx.mem = np.frombuffer(data[lo:hi], np.uint8)
-        n = ctx.fastq_lines(ctx.BASE, hi - lo, lo, lo, hi, size, first=k == 0)
+        ctx, d_buf = make_part(k, lo, hi, hi)
+        n = ctx.fastq_lines(d_buf, hi - lo, lo, lo, hi, size, first=k == 0)
         parts.append(ctx.fastq_reads((-before) % 4, -(-before // 4), every))
         before += n
     return parts
