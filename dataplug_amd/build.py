@@ -1,4 +1,4 @@
-"""Build libdpscan.so, libdpquote.so, libdpfai.so, libdpvpos.so and libdpfq.so in-tree for gfx950:  python -m dataplug_amd.build
+"""Build libdpscan.so, libdpquote.so, libdpfai.so, libdpvpos.so, libdpfq.so and libdpvspan.so in-tree for gfx950:  python -m dataplug_amd.build
 
 The scan library is compiled with -save-temps and the ISA guard (dataplug_amd/isa_guard.py) checks that exact
 device assembly: every kernel, no touched in-flight load destination, no scratch segment.  Only a library that
@@ -34,6 +34,9 @@ VPOS_REQUIRED = ("vpos_parse_kernel", "vpos_reduce_kernel", "vpos_name_kernel") 
 FQ_SRC = os.path.join(HERE, "csrc", "dpfq.hip")            # read lengths and cumulative bases of a FASTQ (include/dpfq.h)
 FQ_OUT = os.path.join(HERE, "lib", "libdpfq.so")
 FQ_REQUIRED = ("fq_read_kernel", "fq_scan_kernel", "fq_sample_kernel")            # what libdpfq.so must contain
+VSPAN_SRC = os.path.join(HERE, "csrc", "dpvspan.hip")      # record ends of a VCF body (include/dpvspan.h)
+VSPAN_OUT = os.path.join(HERE, "lib", "libdpvspan.so")
+VSPAN_REQUIRED = ("vspan_span_kernel", "vspan_blockmax_kernel")                   # what libdpvspan.so must contain
 GZ_SRC = os.path.join(HERE, "csrc", "dpgz.c")
 GZ_PAR_SRC = os.path.join(HERE, "csrc", "dpgz_par.c")     # parallel inflate of one gzip stream
 GZ_OUT = os.path.join(HERE, "lib", "libdpgz.so")            # host-side gzip access-point index (zlib)
@@ -116,6 +119,12 @@ def build_fq(verbose: bool = False) -> str:
     return build(verbose=verbose, out=FQ_OUT, src=FQ_SRC, required=FQ_REQUIRED)
 
 
+def build_vspan(verbose: bool = False) -> str:
+    """libdpvspan.so: the same hipcc line with -save-temps, the ISA guard on that exact assembly (its own kernel
+    list), installed with its ``.isa.json`` stamp only on "ok"."""
+    return build(verbose=verbose, out=VSPAN_OUT, src=VSPAN_SRC, required=VSPAN_REQUIRED)
+
+
 def build_gz() -> str:
     os.makedirs(os.path.dirname(GZ_OUT), exist_ok=True)
     cc = os.environ.get("CC", "gcc")
@@ -132,3 +141,4 @@ if __name__ == "__main__":
     print(build_fai(verbose="-v" in sys.argv))
     print(build_vpos(verbose="-v" in sys.argv))
     print(build_fq(verbose="-v" in sys.argv))
+    print(build_vspan(verbose="-v" in sys.argv))

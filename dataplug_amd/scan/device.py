@@ -60,6 +60,11 @@ Records = namedtuple("Records", "ends table n_quotes n_newlines toggles n")
 VcfPositions = namedtuple("VcfPositions", "n samples run_line run_pos run_last_line run_last names run_offset "
                                           "n_malformed first_malformed n_unsorted first_unsorted first_pos last_pos "
                                           "first_offset malformed_offset unsorted_offset")
+# what ``ScanContext.vcf_spans`` reads back of one part (libdpvspan.so): ``blockmax`` the part's slots (its first and
+# last may be partial K-blocks), the result words, and the byte offsets of the flagged lines: ``first_missing`` /
+# ``first_truncated`` are the lowest such local index or None, ``missing_offset`` / ``truncated_offset`` their lines'.
+VcfSpans = namedtuple("VcfSpans", "n blockmax n_missing first_missing n_truncated first_truncated n_from_end max_span "
+                                  "missing_offset truncated_offset")
 # what ``ScanContext.fastq_reads`` reads back of one part (libdpfq.so).  The part's owned lines are numbered from 0;
 # ``skip`` of them in front belong to a read begun earlier, the device handled the ``n_reads`` reads behind those
 # (global index ``read0`` on) and ``samples`` holds their (offset, bases before it within the launch) pairs.
@@ -71,7 +76,8 @@ FastqPart = namedtuple("FastqPart", "n_lines skip read0 n_reads samples bases n_
                                     "malformed_kind malformed_offset min_len max_len edge_lines edge_starts closed")
 # the libraries that keep a context of their own on a ScanContext's stream, by binding module: the attribute that holds
 # the handle and the prefix of the symbols that create and destroy it (``ScanContext._sub_ctx`` / ``close``)
-_SUB_CTXS = {"_quote": ("_dq", "dq"), "_fai": ("_dfai", "dfai"), "_vpos": ("_dvp", "dvp"), "_fq": ("_dfq", "dfq")}
+_SUB_CTXS = {"_quote": ("_dq", "dq"), "_fai": ("_dfai", "dfai"), "_vpos": ("_dvp", "dvp"), "_fq": ("_dfq", "dfq"),
+             "_vspan": ("_dvs", "dvs")}
 _RECORD_FORMS = {"count": None, "u32": np.uint32, "u64": np.uint64, "u16b": np.uint16}
 
 
@@ -157,6 +163,7 @@ class ScanContext:
         self._dvp = None                              # libdpvpos's dvp_ctx on this context's stream (vcf_positions)
         self._vp = None                               # the resident lines of the last vcf_lines
         self._dfq = None                              # libdpfq's dfq_ctx on this context's stream (fastq_reads)
+        self._dvs = None                              # libdpvspan's dvs_ctx on this context's stream (vcf_spans)
         self._fq = None                               # the resident lines of the last fastq_lines
 
     # ---------------------------------------------------------------- memory
@@ -668,8 +675,8 @@ class ScanContext:
         p = ctypes.c_void_p
         _vpos.check(v.dvp_parse_async(h, p(d_buf), int(buf_len), int(buf_base), int(size), p(d_starts), n, p(d_pos),
                                       p(d_clen), p(d_flags)))
-        self._vp = dict(d_buf=d_buf, buf_len=int(buf_len), buf_base=int(buf_base), d_starts=d_starts, n=n,
-                        d_pos=d_pos, d_clen=d_clen, d_flags=d_flags)
+        self._vp = dict(d_buf=d_buf, buf_len=int(buf_len), buf_base=int(buf_base), size=int(size),
+                        d_starts=d_starts, n=n, d_pos=d_pos, d_clen=d_clen, d_flags=d_flags)
 
     def vcf_lines(self, d_buf: int, buf_len: int, buf_base: int, begin: int, end: int, size: int,
                   first: bool = False, cap: Optional[int] = None) -> int:
@@ -740,6 +747,46 @@ class ScanContext:
                             names, run_offset, int(res[_vpos.R_MALFORMED]), fm, int(res[_vpos.R_UNSORTED]), fu,
                             int(res[_vpos.R_FIRST_POS]), int(res[_vpos.R_LAST_POS]), at(0 if n else None), at(fm),
                             at(fu))
+
+    # ---------------------------------------------------------------- VCF record ends (libdpvspan.so)
+    def _vspan_ctx(self):
+        return self._sub_ctx("_vspan")
+
+    def vspan_geometry(self) -> Tuple[int, int]:
+        """(lines per workgroup of vspan_span_kernel, of vspan_blockmax_kernel) (dvs_geometry)."""
+        from . import _vspan
+        v, h = self._vspan_ctx()
+        a, b = ctypes.c_int(0), ctypes.c_int(0)
+        _vspan.check(v.dvs_geometry(h, ctypes.byref(a), ctypes.byref(b)))
+        return int(a.value), int(b.value)
+
+    def vcf_spans(self, ordinal0: int, every: int) -> VcfSpans:
+        """The span launch (vspan_span_kernel) and the block-max launch (vspan_blockmax_kernel) over the lines the last
+        ``vcf_lines`` / ``vcf_parse`` left resident -- their starts and their parsed POS -- line 0 of which has the
+        global ordinal ``ordinal0`` (include/dpvspan.h).  Only the slots, the result words and the offsets of the
+        flagged lines are read back."""
+        from . import _vspan
+        v, h = self._vspan_ctx()
+        s = self._vp
+        n, k = s["n"], int(every)
+        ns = (ordinal0 + n - 1) // k - ordinal0 // k + 1 if n else 0
+        ws = self.workspace("vspan_lines", 5 * n + 64)
+        d_end, d_flags = ws.ptr, ws.ptr + 4 * n
+        wo = self.workspace("vspan_out", 8 * _vspan.R_WORDS + 4 * ns + 64)
+        d_res, d_max = wo.ptr, wo.ptr + 8 * _vspan.R_WORDS
+        p = ctypes.c_void_p
+        _vspan.check(v.dvs_span_async(h, p(s["d_buf"]), s["buf_len"], s["buf_base"], int(s["size"]), p(s["d_starts"]),
+                                      n, p(s["d_pos"]), p(d_end), p(d_flags)))
+        _vspan.check(v.dvs_blockmax_async(h, p(d_end), p(d_flags), p(s["d_pos"]), n, int(ordinal0), k, p(d_max),
+                                          p(d_res)))
+        out = self.d2h(np.empty(8 * _vspan.R_WORDS + 4 * ns, np.uint8), d_res)
+        res, slots = out[:8 * _vspan.R_WORDS].view(np.uint64), out[8 * _vspan.R_WORDS:].view(np.uint32).copy()
+        none = np.uint64(_vspan.DVS_NONE)
+        low = lambda w: None if res[w] == none else int(res[w])
+        at = lambda i: None if i is None else int(self.d2h(np.empty(1, np.uint64), s["d_starts"] + 8 * i)[0])
+        fm, ft = low(_vspan.R_MIN_MISSING), low(_vspan.R_MIN_TRUNCATED)
+        return VcfSpans(n, slots, int(res[_vspan.R_MISSING]), fm, int(res[_vspan.R_TRUNCATED]), ft,
+                        int(res[_vspan.R_FROM_END]), int(res[_vspan.R_MAX_SPAN]), at(fm), at(ft))
 
     # ---------------------------------------------------------------- FASTQ reads (libdpfq.so)
     def _fq_ctx(self):

@@ -10,6 +10,7 @@ from __future__ import annotations
 import concurrent.futures as cf
 import os
 import threading
+from collections import namedtuple
 from dataclasses import dataclass
 from functools import partial
 from typing import List, Optional, Sequence, Tuple
@@ -1039,6 +1040,16 @@ def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Option
     lines before the part, which the parts chain on the host (``PartChain``, like ``record_index_object``'s
     parities).  ``scan.vpos.merge_parts`` joins the parts."""
     from . import vpos
+    out, _, size = _pos_parts(co, body_offset, every, max_devices, part_bytes, halo, False)
+    return vpos.merge_parts(out, size)
+
+
+def _pos_parts(co, body_offset: int, every: int, max_devices, part_bytes: int, halo: int, spans: bool):
+    """The part-wise pass behind ``pos_index_object`` and ``span_index_object``: (the parts' ``VcfPositions``, their
+    ``vspan.SpanPart`` or None, the object's size).  With ``spans`` each part also runs its span and block-max launches
+    (``ScanContext.vcf_spans``) over the lines that are resident anyway, so the body is fetched once for both indexes;
+    a part's last line that the buffer cut is read with ranged GETs and resolved by the definition on the host."""
+    from . import vspan
     size = int(co.size)
     every = int(every)
     if every < 1 or every & (every - 1):
@@ -1046,11 +1057,12 @@ def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Option
     if halo < 1024:
         raise ValueError("the halo must hold a line's prefix (VPOS_PREFIX_MAX = 1024 bytes)")
     if size <= body_offset:
-        return vpos.merge_parts([], size)
+        return [], [], size
     devs = devices(max_devices, co)
     bounds = line_parts(body_offset, size, len(devs), part_bytes)
     chain = PartChain(len(bounds), "position index")
     out = [None] * len(bounds)
+    sp = [None] * len(bounds)
 
     def run(k: int, _):
         lo, hi = bounds[k]
@@ -1058,10 +1070,82 @@ def pos_index_object(co, body_offset: int, every: int = 128, max_devices: Option
         top = min(size, hi + halo)
         dp = _resident(ctx, co, lo, top)
         chain.publish(k, ctx.vcf_lines(dp, top - lo, lo, lo, hi, size, first=k == 0))
-        out[k] = ctx.vcf_positions(chain.before(k), every)
+        before = chain.before(k)
+        out[k] = ctx.vcf_positions(before, every)
+        if spans:
+            vs = ctx.vcf_spans(before, every)
+            line = read_line(co, vs.truncated_offset, size) if vs.n_truncated else None
+            sp[k] = vspan.fold_line(vs, before, every, line)
 
     run_parts(devs, len(bounds), run, chain)
-    return vpos.merge_parts(out, size)
+    return out, sp, size
+
+
+def read_line(co, offset: int, size: int, window: int = 64 << 10) -> bytes:
+    """The bytes of the line that starts at object byte ``offset``, without its '\n': ranged GETs of growing
+    windows."""
+    got, pos = [], int(offset)
+    while pos < size:
+        hi = min(size, pos + window)
+        raw = co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key, Range=f"bytes={pos}-{hi - 1}")["Body"].read()
+        k = raw.find(b"\n")
+        if k >= 0:
+            got.append(raw[:k])
+            break
+        got.append(raw)
+        pos, window = hi, window * 4
+    return b"".join(got)
+
+
+# ------------------------------------------------------------------------------------------ VCF record-end index
+SpanIndex = namedtuple("SpanIndex", "samples names rows num_lines ends max_span error")
+
+
+def contig_head_ends(co, rows, every: int, window: int = 64 << 10) -> List[int]:
+    """Per contig run, the largest rec_end of its lines inside its first K-block when that block begins in the contig
+    before (first_line % K != 0), else 0.  The slot of such a block also covers the other contig's last lines, so a
+    query takes this value in its place.  At most K - 1 lines a contig, read with ranged GETs from the contig's offset
+    and put through the definition on the host."""
+    from . import vspan
+    out = []
+    for r in rows:
+        l0, n, off, end = int(r["first_line"]), int(r["num_lines"]), int(r["offset"]), int(r["end"])
+        need = min(n, -l0 % every)
+        best, win = 0, window
+        while need:
+            hi = min(end, off + win)
+            raw = co.storage.get_object(Bucket=co.path.bucket, Key=co.path.key, Range=f"bytes={off}-{hi - 1}")["Body"].read()
+            lines = raw.split(b"\n")
+            if hi < end:
+                lines.pop()                                  # the window cut this one
+            if len(lines) >= need or hi >= end:
+                best = max(vspan.rec_end(ln, vspan.line_pos(ln))[0] for ln in lines[:need])
+                break
+            win *= 4
+        out.append(int(best))
+    return out
+
+
+def span_index_object(co, body_offset: int, every: int = 128, max_devices: Optional[int] = None,
+                      part_bytes: int = 2 << 30, halo: int = _HALO0) -> "SpanIndex":
+    """The position index and the record-end index of a VCF body in one pass (include/dpvpos.h, include/dpvspan.h): a
+    ``SpanIndex`` of what ``pos_index_object`` returns -- ``samples``, ``names``, ``rows``, ``num_lines`` -- plus
+    ``ends``, the largest rec_end of every ``every``-block of lines as uint32, and ``max_span``, the body's largest
+    rec_end - POS.  The parts and their cuts are ``pos_index_object``'s; each resident part runs the span and block-max
+    launches behind its parse, so the body is not fetched again.  ``scan.vspan.merge_parts`` joins the parts' slots.
+
+    A body the position index refuses raises its ``VcfFormatError``.  A MISSING_REF line does not raise here: the
+    position index is whole, ``ends`` is None and ``error`` holds the ``VcfFormatError("missing REF", ordinal, offset)``
+    of the first such line, for the caller to raise once the position index is stored."""
+    from . import vpos, vspan
+    out, sp, size = _pos_parts(co, body_offset, every, max_devices, part_bytes, halo, True)
+    samples, names, rows, n = vpos.merge_parts(out, size)
+    try:
+        ends, max_span, n_span = vspan.merge_parts(sp, every)
+    except vpos.VcfFormatError as e:
+        return SpanIndex(samples, names, rows, n, None, None, e)
+    assert n_span == n
+    return SpanIndex(samples, names, rows, n, ends, max_span, None)
 
 
 # ------------------------------------------------------------------------------------------ FASTQ read index

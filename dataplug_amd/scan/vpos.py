@@ -14,13 +14,14 @@ from .fai import first_duplicate
 
 CONTIG_DTYPE = np.dtype([("first_line", "<u8"), ("num_lines", "<u8"), ("offset", "<u8"), ("end", "<u8"),
                          ("min_pos", "<u4"), ("max_pos", "<u4")])
-KINDS = ("malformed", "unsorted", "split contig")
+KINDS = ("malformed", "unsorted", "split contig", "missing REF")
 
 
 class VcfFormatError(ValueError):
     """The body cannot be indexed by position: ``kind`` is "malformed" (a line without CHROM and a POS of 1-10 digits
     <= 2**31 - 1 inside its first 1024 bytes), "unsorted" (POS decreases inside a contig) or "split contig" (the
-    lines of a contig are not contiguous).  ``ordinal`` and ``offset`` are the first offending line's number in the
+    lines of a contig are not contiguous); with ``span_index`` also "missing REF" (a line with fewer than 4 fields or an
+    empty field 4).  ``ordinal`` and ``offset`` are the first offending line's number in the
     body and its byte offset in the object."""
 
     def __init__(self, kind: str, ordinal: int, offset: int):

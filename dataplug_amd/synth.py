@@ -287,6 +287,91 @@ def vcf_sorted(size: int, seed: int = 0, contigs: int = 8, block: int = 4 * 2**2
     return out
 
 
+def gvcf(size: int, seed: int = 0, contigs: int = 8, block: int = 4 * 2**20 - 333,
+         del_every: int = 5000) -> np.ndarray:
+    """A position-sorted gVCF of exactly ``size`` bytes: ``vcf``'s header, one sample column, CHROM constant within a
+    block of rows (``chr1``, ``chr2``, ... in order) and POS never decreasing within a contig.  About seven rows in
+    ten are reference blocks (``<NON_REF>``, ``END=`` one base in front of the next row's POS), two are SNVs, one is a
+    deletion with a REF of 2 to 60 bases, and about one row in ``del_every`` (5,000) is a ``<DEL>`` whose ``END=``
+    (behind ``SVTYPE=DEL;``) lies 10^4 to 10^6 beyond its POS.
+
+    Each contig is one seeded tile of rows repeated, as in ``vcf_sorted``: POS and END are written as ten digits, the
+    copy's number in the first three and the tile's own seven-digit position behind them, so a copy is the tile's
+    bytes with three digits patched per number.  The last row's last field is padded to the exact size; ends with
+    ``\\n``."""
+    body = size - len(VCF_HEADER)
+    share = body // max(1, contigs)
+    if contigs < 1 or share < 512:
+        raise ValueError(f"gvcf needs at least {len(VCF_HEADER) + 512 * max(1, contigs)} bytes")
+    tile_bytes = max(min(block, share), share // 200 + 1)
+    if tile_bytes > 32 << 20:
+        raise ValueError("gvcf: a contig of this size needs more than 200 copies of a 32 MiB tile")
+    rng = np.random.default_rng(seed)
+    m = tile_bytes // 40 + 8                                  # more rows than the tile can hold (a row has >= 40 bytes)
+    v = rng.integers(0, 1 << 30, (m, 6))
+    top = max(2, min(200, 8_900_000 // m))
+    step = 1 + v[:, 0] % top                                  # the distance to the next row's POS
+    rel = np.concatenate(([1], 1 + np.cumsum(step)[:-1]))
+    bases = b"ACGT"
+    rows, patches = [], []                                    # per row: its bytes behind "chrN\t000", and the offsets
+    for j in range(m):                                        # of the copy digits of its END (if it has one)
+        kind, r = int(v[j, 1] % 10), int(rel[j])
+        ref = bases[v[j, 2] % 4:v[j, 2] % 4 + 1]
+        gq = int(v[j, 3] % 99)
+        if v[j, 4] % del_every == 0:
+            head = b"%07d\t.\t%s\t<DEL>\t%d\tPASS\tSVTYPE=DEL;END=" % (r, ref, gq)
+            tail = b"000%07d;SVLEN=-1\tGT:GQ\t0/1:%d\n" % (r + 10**4 + int(v[j, 5] % (10**6 - 10**4 + 1)), gq)
+        elif kind < 7:
+            head = b"%07d\t.\t%s\t<NON_REF>\t.\t.\tEND=" % (r, ref)
+            tail = b"000%07d\tGT:DP:GQ\t0/0:%d:%d\n" % (r + int(step[j]) - 1, int(v[j, 5] % 60), gq)
+        elif kind < 9:
+            head = b"%07d\trs%d\t%s\t%s,<NON_REF>\t%d\tPASS\tDP=%d;AF=0.%d\tGT:GQ\t0/1:%d\n" % (
+                r, int(v[j, 5] % 10**7), ref, bases[(v[j, 2] + 1) % 4:(v[j, 2] + 1) % 4 + 1], gq, int(v[j, 3] % 40),
+                int(v[j, 5] % 1000), gq)
+            tail = None
+        else:
+            n = 2 + int(v[j, 5] % 59)
+            head = b"%07d\t.\t%s\t%s\t%d\tPASS\tDP=%d\tGT:GQ\t1/1:%d\n" % (
+                r, (bases * 16)[v[j, 2] % 4:v[j, 2] % 4 + n], ref, gq, int(v[j, 3] % 40), gq)
+            tail = None
+        patches.append(len(head) if tail is not None else -1)
+        rows.append(head + (tail or b""))
+    tlen = np.fromiter((len(t) for t in rows), np.int64, m)
+    end_at = np.asarray(patches, np.int64)
+    out = np.empty(size, np.uint8)
+    out[:len(VCF_HEADER)] = np.frombuffer(VCF_HEADER, np.uint8)
+    p = len(VCF_HEADER)
+    for c in range(contigs):
+        pre = b"chr%d\t000" % (c + 1)
+        ends = np.cumsum(tlen + len(pre))
+        nrows = max(1, int(np.searchsorted(ends, tile_bytes, "right")))
+        tile = np.frombuffer(b"".join(pre + t for t in rows[:nrows]), np.uint8)
+        row0 = np.concatenate(([0], ends[:nrows - 1]))
+        digit0 = row0 + len(pre) - 3                          # each row's copy digits of POS in the tile
+        has = end_at[:nrows] >= 0
+        digit1 = (row0 + len(pre) + end_at[:nrows])[has]      # and of END, for the rows that have one
+        rows_with = np.flatnonzero(has)
+        limit = size if c == contigs - 1 else len(VCF_HEADER) + share * (c + 1)
+        k = 0
+        while p < limit:
+            nr = nrows if p + len(tile) <= limit else int(np.searchsorted(ends[:nrows], limit - p, "right"))
+            if nr == 0:
+                break
+            if k > 213:
+                raise ValueError("gvcf: more than 214 copies of a tile in one contig")
+            n = int(ends[nr - 1])
+            out[p:p + n] = tile[:n]
+            d1 = digit1[:int(np.searchsorted(rows_with, nr, "left"))]
+            for d, ch in enumerate(b"%03d" % k):
+                out[p + digit0[:nr] + d] = ch
+                out[p + d1 + d] = ch
+            p += n
+            k += 1
+    out[p - 1:size - 1] = ord("x")                            # the last row's last field padded to the exact size
+    out[size - 1] = 10
+    return out
+
+
 def fastq(n_reads: int, seed: int = 0, read_len: int = 100) -> np.ndarray:
     """``n_reads`` 4-line FASTQ reads (inflated stream)."""
     rng = np.random.default_rng(seed)
